@@ -6,7 +6,20 @@ decoder, joint CTC/attention loss) on 16 synthetic 15 s clips per GPU (T = 375 A
 L = 40 labels), train mode (dropouts on), bf16 compute / fp32 master weights.
 Inputs are resident in HBM before the timed region (SURVEY.md §8(d) d1 recipe).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write
+the outputs (--dump-outputs) and print the result line (metric, value, ms_per_step, the in-step
+`roofline` probe and the timed steps' own bookkeeping). Every other measurement (per-modality
+step times, the front end, the isolated encoder GEMM table, the CPU baselines, decode
+throughput) runs after the timed steps under --full only; --quick / --no-cpu-baseline /
+--no-decode leave parts of it out and are refused without --full.
+
+--dump-outputs DIR writes what the last timed step handed back, as float32 DIR/<name>.npy:
+`loss` (the step's loss vector) and fixed seeded samples of the updated fp32 master parameters
+(`param_sample`) and AdamW moments (`exp_avg_sample`, `exp_avg_sq_sample`). Inputs, weights,
+dropout seeds and the modality schedule depend on the arguments only, so two builds run with the
+same arguments can be compared array for array.
 
 With N > 1 and no torch.distributed.run environment (WORLD_SIZE unset) this process is only
 a launcher: it never touches the GPU, starts N child ranks of itself with RANK / WORLD_SIZE /
@@ -17,7 +30,7 @@ non-zero if any rank fails (reference: torchrun over script/train.py:23,259-308)
 Prints ONE JSON line (rank 0). `roofline` is measured live on the probe kernel (the encoder
 FFN up-projection GEMM, 6000x4096x1024 bf16, 24 launches per step) from in-kernel
 s_memrealtime stamps (first workgroup start to last workgroup end of each launch);
-`cpu_baseline` times the repo's CPU restatement of the same model (oracle/, "port") on the
+`cpu_baseline` (--full) times the repo's CPU restatement of the same model (oracle/, "port") on the
 host cores on a bounded sample. `--cpu-selftest` (no GPU, gloo) exercises the launcher and the
 bucketed all-reduce only — it measures nothing and is what the CPU test suite runs.
 """
@@ -325,6 +338,25 @@ def decode_throughput(dev, state_cpu, model_cfg, cpu_threads):
     return out
 
 
+# ============================================================================ outputs
+DUMP_SAMPLE = 1 << 20      # elements per sampled array (4 MiB each as float32)
+
+
+def dump_outputs(path, out4, arena):
+    """--dump-outputs: what the last timed step handed back, as float32 .npy files under `path`:
+    its loss vector, and the same fixed sample (seeded, independent of --seed) of the updated
+    fp32 master parameters and both AdamW moments. The caller has synchronised the device, so an
+    overlapped update has finished."""
+    os.makedirs(path, exist_ok=True)
+    n = arena.data.numel()
+    idx = np.sort(np.random.Generator(np.random.PCG64(20240229)).integers(0, n, size=min(n, DUMP_SAMPLE)))
+    idx = torch.from_numpy(idx).to(arena.data.device)
+    np.save(os.path.join(path, "loss.npy"), out4.detach().float().cpu().numpy())
+    for name, flat in (("param_sample", arena.data), ("exp_avg_sample", arena.exp_avg),
+                       ("exp_avg_sq_sample", arena.exp_avg_sq)):
+        np.save(os.path.join(path, name + ".npy"), flat.detach().index_select(0, idx).float().cpu().numpy())
+
+
 # ===================================================================== CPU self-test
 def cpu_selftest(args):
     """No GPU: the launcher, rendezvous, barrier + max-over-ranks timing and the bucketed
@@ -392,7 +424,7 @@ def gpu_bench(args):
     cfg = AVHubertAVSRConfig(odim=5049, **kw)
     model = AVHubertAVSR(cfg).train()
     state_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         state_cpu = {k: v.clone() for k, v in model.state_dict().items()}
     model.setup_engine(dev, torch.bfloat16)
     eng = model.avsr.engine()
@@ -496,6 +528,8 @@ def gpu_bench(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     losses = out4.cpu().tolist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out4, arena)
     frames = args.steps * B * T * world
     value = frames / elapsed
     # probe kernel duration from its in-kernel stamps (100 MHz ticks), events beside it
@@ -521,33 +555,44 @@ def gpu_bench(args):
         if rec.get("shape") == [M, N_, K_]:
             traffic = rec["traffic_bytes"]
 
-    # per-modality-variant step time (outside the timed region; every rank forced alike)
-    # back-to-back steps of one variant, like the timed loop (no synchronisation between them:
-    # a synchronised step also pays the pipeline refill); the median of the last three intervals
-    variant_ms = {}
-    for name, forced in (("none", None), ("audio_off", "audio_off"), ("video_off", "video_off")):
-        eng.force_modality = (forced,)
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-        evs[0].record()
-        for j in range(4):
-            step(variant=True)
-            evs[j + 1].record()
-        torch.cuda.synchronize()
-        per = [evs[j].elapsed_time(evs[j + 1]) for j in range(1, 4)]
-        variant_ms[name] = round(sorted(per)[1], 2)
-    eng.force_modality = None
-    exp_ms = expected_step_ms(variant_ms, world)
-    # what one seeded draw of the reference's RNG would have given for the same K steps
-    # (per-variant medians; the timed region itself runs the stratified schedule)
-    rs = np.random.RandomState(args.seed + 7919 * rank)
-    raw = []
-    for _ in range(args.steps):
-        pm, pa = rs.random_sample(), rs.random_sample()
-        raw.append("none" if pm >= cfg.modality_dropout else ("audio_off" if pa < cfg.audio_dropout else "video_off"))
-    raw_ms = sum(variant_ms[k] for k in raw)
+    def modality_variants():
+        # per-modality-variant step time (outside the timed region; every rank forced alike)
+        # back-to-back steps of one variant, like the timed loop (no synchronisation between them:
+        # a synchronised step also pays the pipeline refill); the median of the last three intervals
+        variant_ms = {}
+        for name, forced in (("none", None), ("audio_off", "audio_off"), ("video_off", "video_off")):
+            eng.force_modality = (forced,)
+            if world > 1:
+                dist.barrier()
+            torch.cuda.synchronize()
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            evs[0].record()
+            for j in range(4):
+                step(variant=True)
+                evs[j + 1].record()
+            torch.cuda.synchronize()
+            per = [evs[j].elapsed_time(evs[j + 1]) for j in range(1, 4)]
+            variant_ms[name] = round(sorted(per)[1], 2)
+        eng.force_modality = None
+        exp_ms = expected_step_ms(variant_ms, world)
+        # what one seeded draw of the reference's RNG would have given for the same K steps
+        # (per-variant medians; the timed region itself runs the stratified schedule)
+        rs = np.random.RandomState(args.seed + 7919 * rank)
+        raw = []
+        for _ in range(args.steps):
+            pm, pa = rs.random_sample(), rs.random_sample()
+            raw.append("none" if pm >= cfg.modality_dropout else ("audio_off" if pa < cfg.audio_dropout else "video_off"))
+        raw_ms = sum(variant_ms[k] for k in raw)
+        return {"step_ms": variant_ms, "p": MODALITY_P,
+                "expected_ms_per_step": round(exp_ms, 3),
+                "value_expected": round(B * T * world / exp_ms * 1e3, 2),
+                "value_seeded_draw": round(args.steps * B * T * world / raw_ms * 1e3, 2),
+                "seeded_draw_counts": {k: raw.count(k) for k in MODALITY_P},
+                "note": "median of 3 back-to-back forced steps per variant (after one lead-in step); value_expected weights them with "
+                        "the reference's draw probabilities (avhubert.py:476-482), slowest rank "
+                        "bounding a step for N > 1; value_seeded_draw: the same K steps under one "
+                        "numpy draw (seed --seed) instead of the stratified schedule"}
+
     allreduce = None
     if world > 1:
         exposed = [j0.elapsed_time(j1) for (c0, c1, j0, j1) in ar_timing]
@@ -585,15 +630,6 @@ def gpu_bench(args):
         "model_tflops_per_s": round(value * fpf / world / 1e12, 1),
         "model_mfu": round(value * fpf / world / 1e12 / BF16_PEAK_TFLOPS, 4),
         "model_flops_note": "algorithmic FLOPs of the steps actually timed (video_off: no ResNet backward)",
-        "modality_variants": {"step_ms": variant_ms, "p": MODALITY_P,
-                              "expected_ms_per_step": round(exp_ms, 3),
-                              "value_expected": round(B * T * world / exp_ms * 1e3, 2),
-                              "value_seeded_draw": round(args.steps * B * T * world / raw_ms * 1e3, 2),
-                              "seeded_draw_counts": {k: raw.count(k) for k in MODALITY_P},
-                              "note": "median of 3 back-to-back forced steps per variant (after one lead-in step); value_expected weights them with "
-                                      "the reference's draw probabilities (avhubert.py:476-482), slowest rank "
-                                      "bounding a step for N > 1; value_seeded_draw: the same K steps under one "
-                                      "numpy draw (seed --seed) instead of the stratified schedule"},
         "loss": [round(x, 4) for x in losses],
         "host_ms_per_step_timed": round(sum(host_t) / len(host_t) * 1e3, 2),
         "host_ms_steps": [round(t * 1e3, 1) for t in host_t],
@@ -608,6 +644,13 @@ def gpu_bench(args):
     }
     if forced_all is not None:
         result["forced_modality"] = f"every timed step forced to {args.force_modality} (profiling run, not the metric)"
+    if not args.full:                    # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return 0
+    result["modality_variants"] = modality_variants()
     if rank == 0 and not args.quick:
         result["frontend"] = frontend_timing(B, T, dev)
         if args.layers is None:
@@ -639,14 +682,20 @@ def main():
     ap.add_argument("--batch", type=int, default=16, help="clips per GPU")
     ap.add_argument("--seq", type=int, default=375, help="AV-frames per clip (15 s at 25 fps)")
     ap.add_argument("--labels", type=int, default=40)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss vector, seeded samples of the updated "
+                         "parameters and AdamW moments) as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-modality step times, the front end, the "
+                         "isolated encoder GEMMs, the CPU baselines and decode throughput (minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--modality-draws", choices=["stratified", "random"], default="stratified",
                     help="timed steps' modality variants: stratified to the reference's probabilities (default), "
                          "or drawn from numpy's global RNG per forward as the reference does")
     ap.add_argument("--grad-compress", choices=["bf16"], default=None,
                     help="N > 1: exchange gradients in bf16 (parallel.GradReducer; default fp32 for parity)")
-    ap.add_argument("--no-decode", action="store_true", help="skip the C1/C4/C5 decode throughput section")
-    ap.add_argument("--quick", action="store_true", help="only the step measurement (profiling runs)")
+    ap.add_argument("--no-decode", action="store_true", help="--full: skip the C1/C4/C5 decode throughput section")
+    ap.add_argument("--quick", action="store_true", help="--full: only the step and per-modality measurements (profiling runs)")
     ap.add_argument("--layers", type=int, default=None, help="debug only: fewer encoder layers (INVALID for the metric)")
     ap.add_argument("--seed", type=int, default=1234, help="seeds the inputs, dropout streams and the "
                     "modality-dropout draws (numpy global RNG, as the reference draws them)")
@@ -654,6 +703,8 @@ def main():
                     help="profiling only: every step uses this modality variant (the value is then not the metric)")
     ap.add_argument("--cpu-selftest", action="store_true", help="no GPU: launcher + gloo all-reduce check only")
     args = ap.parse_args()
+    if not args.full and (args.quick or args.no_decode or args.no_cpu_baseline):
+        ap.error("--quick, --no-decode and --no-cpu-baseline trim --full: give --full with them")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, sys.argv[1:])
     if args.cpu_selftest:

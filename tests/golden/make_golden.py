@@ -2,7 +2,7 @@
 mounted read-only at /root/reference) on CPU, fp32, in this container.
 
 Never run on the GPU box (the reference does not travel); only its outputs are committed:
-  tests/golden/avsr_tiny.npz   — see the `out[...]` keys below.
+  tests/golden/avsr_tiny.N.npz (tests/golden/parts.py) — see the `out[...]` keys below.
 
 Recipe: tiny AVHubertAVSRConfig (oracle/weights.py TINY_CONFIG) with all
 dropouts 0, weights from oracle/weights.py gen_tensor(key, shape, seed=0), inputs from
@@ -24,6 +24,7 @@ sys.path.insert(0, "/root/reference")
 sys.dont_write_bytecode = True
 
 from oracle.weights import NO_DROPOUT, TINY_CONFIG, collate, gen_tensor, make_inputs  # noqa: E402
+from tests.golden.parts import save_parts  # noqa: E402
 
 
 def main():
@@ -103,9 +104,8 @@ def main():
             out[f"onestep_{b}"] = logp.numpy()
             out[f"ctc_logp_{b}"] = model.avsr.ctc.log_softmax(x.unsqueeze(0)).numpy()
 
-    path = os.path.join(HERE, "avsr_tiny.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes")
+    for path in save_parts("avsr_tiny", out):
+        print("wrote", path, os.path.getsize(path), "bytes")
     print("loss", out["loss"], "yseq", out["yseq_b1_0"][:10], out["yseq_b3_1"][:10])
 
 

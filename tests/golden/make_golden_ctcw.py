@@ -10,7 +10,7 @@ get_beam_search_decoder(model, token_list, ctc_weight, beam_size)
   ctc_weight = 1.0: the CTC prefix scorer alone over the FULL vocabulary
                     (pre_beam_score_key=None; the decoder's weight is 0).
 Model: the tiny recipe (oracle/weights.py TINY_CONFIG, gen_tensor weights, seed 0, dropouts 0,
-eval); inputs: the reference's own encoder outputs stored in avsr_tiny.npz (dec_enc_0 / _1).
+eval); inputs: the reference's own encoder outputs stored in avsr_tiny.N.npz (dec_enc_0 / _1).
 Stored per (ctc weight, beam, clip): EVERY returned hypothesis (token sequence, total score,
 per-scorer scores).
 
@@ -30,6 +30,7 @@ sys.path.insert(0, "/root/reference")
 sys.dont_write_bytecode = True
 
 from oracle.weights import NO_DROPOUT, TINY_CONFIG, gen_tensor  # noqa: E402
+from tests.golden.parts import load_parts  # noqa: E402
 
 WEIGHTS = (0.0, 1.0)
 BEAMS = (1, 3)
@@ -46,7 +47,7 @@ def main():
     sd = model.state_dict()
     model.load_state_dict({k: torch.from_numpy(gen_tensor(k, v.shape, seed=0)) for k, v in sd.items()}, strict=True)
     model.eval()
-    g = np.load(os.path.join(HERE, "avsr_tiny.npz"), allow_pickle=False)
+    g = load_parts("avsr_tiny")
     token_list = ["<blank>"] + [f"u{i}" for i in range(1, 5048)] + ["<eos>"]
     out = {}
     for w in WEIGHTS:

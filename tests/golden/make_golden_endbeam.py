@@ -8,7 +8,7 @@ With the recipe weights every C1 search runs to maxlen (random decoder logits ne
 ended at different lengths (src/nets/beam_search.py:330-406, post_process :408-456) were never
 exercised against the reference. Here the full-size model's recipe weights get
 `avsr.decoder.output_layer.bias[eos] += EOS_BIAS` for a few offsets, and the reference's own C1
-encoder output (avsr_full.npz "c1_enc") is decoded with beams 3 and 5
+encoder output (avsr_full.N.npz "c1_enc") is decoded with beams 3 and 5
 (get_beam_search_decoder, ctc_weight 0.1). Stored per (offset, beam, clip): EVERY returned
 hypothesis (the reference returns all ended hypotheses, best first) — token sequences and
 total / decoder / ctc scores — and the step at which the search stopped.
@@ -30,6 +30,7 @@ sys.dont_write_bytecode = True
 
 from oracle.weights import NO_DROPOUT, gen_tensor  # noqa: E402
 from tests.golden.full_inputs import ENDBEAM  # noqa: E402
+from tests.golden.parts import load_parts  # noqa: E402
 
 
 def main():
@@ -43,7 +44,7 @@ def main():
     sd = model.state_dict()
     model.load_state_dict({k: torch.from_numpy(gen_tensor(k, v.shape, seed=0)) for k, v in sd.items()}, strict=True)
     model.eval()
-    enc = torch.from_numpy(np.load(os.path.join(HERE, "avsr_full.npz"), allow_pickle=False)["c1_enc"])
+    enc = torch.from_numpy(load_parts("avsr_full")["c1_enc"])
     token_list = ["<blank>"] + [f"u{i}" for i in range(1, 5048)] + ["<eos>"]
     eos = model.avsr.eos
     bias = model.avsr.decoder.output_layer.bias

@@ -2,7 +2,7 @@
 mounted read-only at /root/reference) on CPU, fp32, in this container.
 
 Never run on the GPU box (the reference does not travel); only its outputs are committed:
-  tests/golden/avsr_full.npz
+  tests/golden/avsr_full.N.npz (parts, tests/golden/parts.py)
 
 Model: the BASELINE configs' model, AVHubertAVSRConfig(odim=5049) (24 encoder layers, 6
 decoder layers, 428 M parameters), weights from oracle/weights.py gen_tensor(key, shape,
@@ -38,6 +38,7 @@ sys.dont_write_bytecode = True
 
 from oracle.weights import NO_DROPOUT, collate, gen_tensor, make_inputs  # noqa: E402
 from tests.golden.full_inputs import C1, DEC_ROWS, ENC_ROWS, TR, TR_LABELS  # noqa: E402
+from tests.golden.parts import save_parts  # noqa: E402
 
 def digest(*arrays):
     h = hashlib.sha256()
@@ -126,9 +127,9 @@ def main():
     out["bn_keys"] = np.array(rkeys)
     out["bn_after"] = np.stack([np.pad(bufs[k].flatten()[:8].numpy(), (0, 8 - min(8, bufs[k].numel()))) for k in rkeys])
 
-    path = os.path.join(HERE, "avsr_full.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, os.path.getsize(path), "bytes in", round(time.time() - t0, 1), "s")
+    for path in save_parts("avsr_full", out):
+        print("wrote", path, os.path.getsize(path), "bytes")
+    print("in", round(time.time() - t0, 1), "s")
 
 
 if __name__ == "__main__":

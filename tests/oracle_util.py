@@ -6,12 +6,11 @@ import torch
 
 from oracle import avsr_oracle as O
 from oracle.weights import TINY_CONFIG, collate, gen_tensor
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "avsr_tiny.npz")
+from tests.golden.parts import load_parts
 
 
 def load_golden():
-    return dict(np.load(GOLDEN, allow_pickle=False))
+    return load_parts("avsr_tiny")          # tests/golden/avsr_tiny.N.npz
 
 
 def golden_state(g, seed=0):
@@ -29,12 +28,11 @@ def tiny_cfg():
 
 
 # ---------------------------------------------------------------------------- full size
-GOLDEN_FULL = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "avsr_full.npz")
 TOKENS = ["<blank>"] + [f"u{i}" for i in range(1, 5048)] + ["<eos>"]
 
 
 def load_golden_full():
-    return dict(np.load(GOLDEN_FULL, allow_pickle=False))
+    return load_parts("avsr_full")          # tests/golden/avsr_full.N.npz
 
 
 def full_state(g, seed=0):

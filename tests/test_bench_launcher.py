@@ -69,3 +69,45 @@ def test_stratified_variants_match_reference_probabilities():
             blk = s[i:i + 4]
             assert blk.count(None) == 2 and blk.count("video_off") == 1 and blk.count("audio_off") == 1
     assert bench.stratified_variants(4, 0) != bench.stratified_variants(4, 1)
+
+
+def test_dump_outputs_writes_the_same_float32_sample(tmp_path):
+    """--dump-outputs: the loss vector and one fixed sample (same indices for parameters and
+    both moments, independent of the run) as float32 .npy files"""
+    sys.path.insert(0, ROOT)
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    n = 3 * bench.DUMP_SAMPLE + 17
+    base = torch.arange(n, dtype=torch.float32)
+    arena = types.SimpleNamespace(data=base, exp_avg=-base, exp_avg_sq=base * 2)
+    out4 = torch.tensor([4.0, 3.0, 1.0, 0.5], dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out4, arena)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["exp_avg_sample.npy", "exp_avg_sq_sample.npy", "loss.npy", "param_sample.npy"]
+    a = {k: np.load(tmp_path / "a" / k) for k in names}
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss.npy"].tolist() == [4.0, 3.0, 1.0, 0.5]
+    p = a["param_sample.npy"]
+    assert p.shape == (bench.DUMP_SAMPLE,) and p.min() >= 0 and p.max() < n and len(np.unique(p)) > p.size // 2
+    assert np.array_equal(a["exp_avg_sample.npy"], -p) and np.array_equal(a["exp_avg_sq_sample.npy"], 2 * p)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in names:
+        assert np.array_equal(a[k], np.load(tmp_path / "b" / k))
+
+
+@pytest.mark.parametrize("flag", ["--quick", "--no-decode", "--no-cpu-baseline"])
+def test_full_trimming_flags_need_full(flag, monkeypatch, capsys):
+    """the flags that leave parts of --full out are refused without it (exit status 2 before any
+    work), so a caller written for the earlier default fails loudly"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", flag])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+    assert "--full" in capsys.readouterr().err

@@ -21,7 +21,7 @@ for prog in ${PROGS:-probe wgrad attn stem cwgrad step}; do
     stem) CMD="python3 tools/stem_kbench.py 5";;
     stemw) CMD="python3 tools/stem_wgrad_kbench.py 3";;
     cwgrad) CMD="python3 tools/wgrad_kb.py";;
-    step) CMD="python3 bench.py --steps 2 --warmup 1 --quick --no-cpu-baseline --force-modality none";;
+    step) CMD="python3 bench.py --steps 2 --warmup 1 --full --quick --no-cpu-baseline --force-modality none";;
   esac
   for pass in A B; do
     if [ $pass = A ]; then P="$PA"; else P="$PB"; fi

@@ -40,7 +40,7 @@ def load_rows(path):
 
 rows = sorted(load_rows(path), key=lambda r: int(r["Start_Timestamp"]))
 ends = step_ends(rows)
-# --skip S: leave out the last S steps (bench --quick appends 12 per-variant steps: none x4,
+# --skip S: leave out the last S steps (bench --full --quick appends 12 per-variant steps: none x4,
 # audio_off x4, video_off x4, one lead-in + 3 timed each; the forced timed steps are the 4 before them)
 skip = int(sys.argv[sys.argv.index("--skip") + 1]) if "--skip" in sys.argv else 0
 if skip:
