@@ -271,7 +271,7 @@ class BatchBeamSearch:
         Tm = max(Ts)
         maxlens = [T if maxlenratio == 0 else (-int(maxlenratio) if maxlenratio < 0 else max(1, int(maxlenratio * T)))
                    for T in Ts]
-        D, P, beam = eng.dD, self.pre_beam_size, self.beam_size
+        D = eng.dD
         ar = eng.arena
         # padded memory [U][Tm][D] -> CTC log-probs [U][Tm][V] and per-layer cross K/V [U*Tm][2D]
         xp = torch.zeros(U, Tm, D, device=dev, dtype=eng.dtype)
@@ -293,8 +293,31 @@ class BatchBeamSearch:
         logp = torch.empty(U, Tm, eng.V, device=dev, dtype=torch.float32)
         ops.log_softmax_rows(cl, eng.V, logp.view(U * Tm, eng.V))
         steps = max(maxlens)
+        eng.ensure_pe(steps + 1)
+        st = self._new_state(dev, eng.dtype, Ts, maxlens, logp, mem, D, eng.dl, end_detect=int(maxlenratio == 0.0),
+                             fold=self._fold_layernorms(eng) if FOLD_LN and self.use_dec else None)
+        self._step(eng, st, True, 0)           # step 0: CTC state from scratch; reads ancestry 0, writes 1
+        if steps > 1:
+            graphs = self._capture(eng, st)
+            done_host = st["done"][U:]
+            for i in range(1, steps):
+                graphs[i & 1].replay()         # step i reads ping-pong buffer i & 1
+                if i % 8 == 0 and int(done_host.item()) == U:
+                    break
+        torch.cuda.current_stream(dev).synchronize()
+        return self._collect(st, xs, maxlenratio, minlenratio)
+
+    def _new_state(self, device, dtype, Ts, maxlens, logp, mem, D, layers, end_detect=1, fold=None):
+        """the device-side search state of U = len(Ts) utterances (Ts frames, maxlens steps each)
+        before step 0: one live hypothesis (sos) per utterance. logp (U, Tm, V) fp32 CTC log-probs,
+        mem per decoder layer the cross-attention K/V [U*Tm][2D]; the self-attention cache is
+        (layers, 2, Lmax*R, D) of `dtype`. Depends on no engine, so a search whose
+        `_decoder_step` is replaced (the scripted-decoder tests) builds it too."""
+        dev = device
+        U, Tm, V = len(Ts), max(Ts), logp.shape[-1]
+        P, beam = self.pre_beam_size, self.beam_size
+        steps = max(maxlens)
         Lmax = steps + 1
-        eng.ensure_pe(Lmax)
         R = U * beam
         i32 = dict(device=dev, dtype=torch.int32)
         f32 = dict(device=dev, dtype=torch.float32)
@@ -303,11 +326,11 @@ class BatchBeamSearch:
         score0 = torch.full((R,), float("-inf"))
         score0[::beam] = 0.0                  # one live hypothesis (sos) per utterance
         st = dict(
-            U=U, R=R, Lmax=Lmax, Tm=Tm, steps=steps, end_detect=int(maxlenratio == 0.0), mem=mem, logp=logp,
+            U=U, R=R, Lmax=Lmax, Tm=Tm, steps=steps, end_detect=int(end_detect), mem=mem, logp=logp,
             pos=torch.zeros(1, **i32), maxlen=torch.tensor(maxlens, dtype=torch.int32).to(dev),
             tok=torch.full((R,), self.sos, **i32), score=score0.to(dev),
             sdec=torch.zeros(R, **f64), sctc=torch.zeros(R, **f64), s_prev=torch.zeros(R, **f32),
-            cache=torch.empty(eng.dl, 2, Lmax * R, D, device=dev, dtype=eng.dtype),
+            cache=torch.empty(layers, 2, Lmax * R, D, device=dev, dtype=dtype),
             anc=[torch.zeros(R, Lmax, **i32), torch.zeros(R, Lmax, **i32)], klen_self=torch.empty(R, **i32),
             uidx=(rows // beam).to(dev), klen_mem=torch.tensor(Ts, dtype=torch.int32)[rows // beam].to(dev),
             tlen=torch.tensor(Ts, dtype=torch.int32).to(dev),
@@ -321,11 +344,11 @@ class BatchBeamSearch:
             end_flag=torch.zeros(steps, R, **i32), end_score=torch.zeros(steps, R, **f32),
             end_dec=torch.zeros(steps, R, **f64), end_ctc=torch.zeros(steps, R, **f64),
             best_len=torch.full((U, Lmax + 3), float("-inf"), **f32), best_end=torch.full((U,), float("-inf"), **f32),
-            done=torch.zeros(U + 1, **i32), fold=self._fold_layernorms(eng) if FOLD_LN and self.use_dec else None)
+            done=torch.zeros(U + 1, **i32), fold=fold)
         if not self.use_ctc:
             st["psi"].zero_()                 # w_ctc = 0 multiplies it: keep it finite
         if not self.use_dec:
-            st["dec0"] = torch.zeros(R, eng.V, **f32)
+            st["dec0"] = torch.zeros(R, V, **f32)
             nch = -(-self.n_vocab // 64)
             ids = torch.arange(nch * 64, dtype=torch.int32)
             ids[ids >= self.n_vocab] = self.blank          # padding ids: blank (psi = LOGZERO)
@@ -333,16 +356,7 @@ class BatchBeamSearch:
             st["psi_c"] = torch.empty(R, 65, **f32)
             st["r_scr"] = torch.empty(R, 64, Tm, 2, **f32)
             st["psi_full"] = torch.empty(R, nch * 64, **f32)
-        self._step(eng, st, True, 0)           # step 0: CTC state from scratch; reads ancestry 0, writes 1
-        if steps > 1:
-            graphs = self._capture(eng, st)
-            done_host = st["done"][U:]
-            for i in range(1, steps):
-                graphs[i & 1].replay()         # step i reads ping-pong buffer i & 1
-                if i % 8 == 0 and int(done_host.item()) == U:
-                    break
-        torch.cuda.current_stream(dev).synchronize()
-        return self._collect(st, xs, maxlenratio, minlenratio)
+        return st
 
     def _capture(self, eng, st):
         """two graphs of the generic step (k = 0, 1): capture records, it does not run. The

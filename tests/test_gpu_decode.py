@@ -44,13 +44,24 @@ def test_dec_attn_matches_torch(dev):
     vh = vc[:, :L].view(n, L, H, 64).transpose(1, 2)
     ref = torch.softmax(qh @ kh.transpose(-1, -2) * 0.125, -1) @ vh
     torch.testing.assert_close(o, ref.reshape(n, D), rtol=1e-5, atol=1e-5)
-    # shared keys (bstride 0), bf16 storage
+    # shared keys (bstride 0)
     mem = torch.randn(L, 2 * D, generator=g).to(dev)
     ops.dec_attn(q[:, :D], mem[:, :D], mem[:, D:], o, n=n, H=H, klen_max=L, k_bstride=0, v_bstride=0)
     km = mem[:, :D].view(L, H, 64).transpose(0, 1)
     vm = mem[:, D:].view(L, H, 64).transpose(0, 1)
     ref = torch.softmax(qh @ km.transpose(-1, -2).unsqueeze(0) * 0.125, -1) @ vm.unsqueeze(0)
     torch.testing.assert_close(o, ref.reshape(n, D), rtol=1e-5, atol=1e-5)
+    # the same in bf16 storage (q, keys, values and the output), against fp64 attention of the
+    # rounded values: one bf16 rounding of the output (2^-9 relative), doubled for an fp32 result
+    # on the other side of a rounding boundary
+    qb, mb = q.bfloat16(), mem.bfloat16()
+    ob = torch.empty(n, D, device=dev, dtype=torch.bfloat16)
+    ops.dec_attn(qb[:, :D], mb[:, :D], mb[:, D:], ob, n=n, H=H, klen_max=L, k_bstride=0, v_bstride=0)
+    qd = qb[:, :D].double().view(n, H, 1, 64)
+    kd = mb[:, :D].double().view(L, H, 64).transpose(0, 1)
+    vd = mb[:, D:].double().view(L, H, 64).transpose(0, 1)
+    refb = (torch.softmax(qd @ kd.transpose(-1, -2).unsqueeze(0) * 0.125, -1) @ vd.unsqueeze(0)).reshape(n, D)
+    assert bool(((ob.double() - refb).abs() <= refb.abs() * 2.0 ** -8 + 1e-4).all())
 
 
 def test_row_topk_and_log_softmax(dev):
