@@ -50,8 +50,21 @@ __global__ __launch_bounds__(NT) void dense_kernel(DenseArgs a) {
   epilogue<T, OutT, WM, WN>(e, m0, n0, acc, smem);
 }
 
+// the epilogue arguments of one output tile's batch / K split, pinned to the variant EV
+template <typename OutT, int EV>
+AVSR_DEV Epi tile_epi(const DenseArgs& a, int bz, int sp) {
+  Epi e = a.e;
+  epi_fold<EV>(e);
+  e.C = (OutT*)e.C + (int64_t)bz * a.sC + sp * a.sSplit;
+  if (e.res) e.res = (const bf16*)e.res + (int64_t)bz * a.sR;
+  if (e.preact) e.preact = (bf16*)e.preact + (int64_t)bz * a.sC;
+  if (e.gate) e.gate = (const bf16*)e.gate + (int64_t)bz * a.sC;
+  e.drop_base = (uint64_t)bz * (uint64_t)a.M * (uint64_t)a.N;
+  return e;
+}
+
 // bf16 LDS-DMA path (gemm_glds.h): GCfg tiles, 1-D XCD-remapped grid
-template <typename OutT, bool AK, bool BK, class CF>
+template <typename OutT, bool AK, bool BK, class CF, int EV = EV_GENERIC>
 __global__ __launch_bounds__(CF::NTH, CF::MINB) void dense_glds_kernel(DenseArgs a, int tiles_m, int tiles_n) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if (a.stamp != nullptr && threadIdx.x == 0) atomicMin(a.stamp, (unsigned long long)__builtin_amdgcn_s_memrealtime());
@@ -77,13 +90,8 @@ __global__ __launch_bounds__(CF::NTH, CF::MINB) void dense_glds_kernel(DenseArgs
     LB lb; lb.init((const bf16*)a.B + (int64_t)bz * a.sB, a.ldb, n0, a.N, kend, wave, lane);
     gemmg::mainloop_glds<CF>(la, lb, kbeg, nk, acc, smem);
   }
-  Epi e = a.e;
-  e.C = (OutT*)e.C + (int64_t)bz * a.sC + sp * a.sSplit;
-  if (e.res) e.res = (const bf16*)e.res + (int64_t)bz * a.sR;
-  if (e.preact) e.preact = (bf16*)e.preact + (int64_t)bz * a.sC;
-  if (e.gate) e.gate = (const bf16*)e.gate + (int64_t)bz * a.sC;
-  e.drop_base = (uint64_t)bz * (uint64_t)a.M * (uint64_t)a.N;
-  gemmg::epilogue_g<bf16, OutT, CF>(e, m0, n0, acc, smem);
+  const Epi e = tile_epi<OutT, EV>(a, bz, sp);
+  gemmg::epilogue_g<bf16, OutT, CF, EV>(e, m0, n0, acc, smem);
   if (a.stamp != nullptr) {   // uniform: every wave's stores issued before the end stamp
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(a.stamp + 1, (unsigned long long)__builtin_amdgcn_s_memrealtime());
@@ -328,11 +336,73 @@ int launch_pp(const DenseArgs& a, int batch, hipStream_t st) {
   return 0;
 }
 
-template <typename OutT, bool AK, bool BK, class CF>
+// The compile-time epilogue variant a launch qualifies for (gemm_core.h EV_*), or EV_GENERIC.
+// A variant puts every vector of every tile on the 8-column path, so the host check covers what
+// epi_vec_ok tests in the kernel with the batch / split offsets applied.
+template <typename OutT>
+int epi_variant(const DenseArgs& a, int batch) {
+  const Epi& e = a.e;
+  if (e.atomic || e.stats || e.rm_wc || e.alpha != 1.f || e.beta != 0.f || (e.N % 8)) return EV_GENERIC;
+  const uintptr_t ptrs = (uintptr_t)e.C | (uintptr_t)e.preact | (uintptr_t)e.res | (uintptr_t)e.gate | (uintptr_t)e.bias;
+  if (ptrs & 15u) return EV_GENERIC;
+  const int64_t so = (int64_t)sizeof(OutT);
+  if (((e.ldc * so) | (e.ldc * 2) | (e.ldr * 2)) & 15) return EV_GENERIC;
+  if (batch > 1 && (((a.sC * so) | (a.sC * 2) | (a.sR * 2)) & 15)) return EV_GENERIC;
+  if (a.splits > 1 && ((a.sSplit * so) & 15)) return EV_GENERIC;
+  const bool drop = e.drop_p > 0.f;
+  if (!e.bwd) {
+    if (e.gate || e.colsum) return EV_GENERIC;
+    if (!e.bias) return (!e.preact && !e.act && !e.res && !drop) ? EV_PLAIN : EV_GENERIC;
+    if (!e.preact && !e.act && !e.res && !drop) return EV_BIAS;
+    if (!e.preact && !e.act && e.res) return EV_BIAS_RES;
+    if (e.preact && e.act == AVSR_ACT_GELU && !e.res) return EV_BIAS_ACT_PRE;
+    return EV_GENERIC;
+  }
+  if (e.bias || e.preact || e.res) return EV_GENERIC;
+  if (e.gate && e.act == AVSR_ACT_GELU) return EV_GATE;
+  if (!e.gate && !e.act && !drop && !e.colsum) return EV_PLAIN;
+  return EV_GENERIC;
+}
+
+// Variants are instantiated where the encoder's GEMMs run them: bf16 output, the forward ones
+// on the forward layout (B k-major), the backward ones on the data-grad layout (B r-contiguous);
+// every other combination runs the generic epilogue.
+template <typename OutT, bool BK, int EV>
+constexpr bool ev_built() {
+  if (EV == EV_GENERIC) return true;
+  if (sizeof(OutT) != 2) return false;
+  return BK ? (EV == EV_BIAS || EV == EV_BIAS_RES || EV == EV_BIAS_ACT_PRE) : (EV == EV_PLAIN || EV == EV_GATE);
+}
+
+template <typename OutT, bool AK, bool BK, class CF, int EV>
+int launch_glds_ev(const DenseArgs& a, int tm, int tn, long nwg, hipStream_t st) {
+  if constexpr (!ev_built<OutT, BK, EV>()) {
+    return launch_glds_ev<OutT, AK, BK, CF, EV_GENERIC>(a, tm, tn, nwg, st);
+  } else {
+    hipLaunchKernelGGL((dense_glds_kernel<OutT, AK, BK, CF, EV>), dim3((unsigned)nwg), dim3(CF::NTH), CF::LDS_BYTES,
+                       st, a, tm, tn);
+    AVSR_CHECK_LAUNCH();
+    return 0;
+  }
+}
+
+// VARIANTS: the configuration carries the compile-time epilogue variants (the encoder's two
+// 192-row tiles, where its GEMM time is; every further instantiation costs build time)
+template <typename OutT, bool AK, bool BK, class CF, bool VARIANTS = false>
 int launch_glds(const DenseArgs& a, int batch, hipStream_t st) {
   const int tm = (a.M + CF::BM - 1) / CF::BM, tn = (a.N + CF::BN - 1) / CF::BN;
   const long nwg = (long)tm * tn * batch * a.splits;
   if (nwg > 0x7fffffffL) return AVSR_E_SHAPE;
+  if constexpr (VARIANTS) {
+    switch (epi_variant<OutT>(a, batch)) {
+      case EV_PLAIN: return launch_glds_ev<OutT, AK, BK, CF, EV_PLAIN>(a, tm, tn, nwg, st);
+      case EV_BIAS: return launch_glds_ev<OutT, AK, BK, CF, EV_BIAS>(a, tm, tn, nwg, st);
+      case EV_BIAS_RES: return launch_glds_ev<OutT, AK, BK, CF, EV_BIAS_RES>(a, tm, tn, nwg, st);
+      case EV_BIAS_ACT_PRE: return launch_glds_ev<OutT, AK, BK, CF, EV_BIAS_ACT_PRE>(a, tm, tn, nwg, st);
+      case EV_GATE: return launch_glds_ev<OutT, AK, BK, CF, EV_GATE>(a, tm, tn, nwg, st);
+      default: break;
+    }
+  }
   hipLaunchKernelGGL((dense_glds_kernel<OutT, AK, BK, CF>), dim3((unsigned)nwg), dim3(CF::NTH), CF::LDS_BYTES, st, a,
                      tm, tn);
   AVSR_CHECK_LAUNCH();
@@ -446,7 +516,7 @@ int launch_cfg(int cfg, const DenseArgs& a, int batch, hipStream_t st) {
     case 16: return launch_glds<OutT, AK, BK, Cfg64>(a, batch, st);
     case 18: return launch_glds<OutT, AK, BK, Cfg64s4>(a, batch, st);
     case 11:   // BM = 192: r-contiguous A needs BM % 64 == 0 (weight-grads stay on 128x128)
-      if constexpr (AK) return launch_glds<OutT, AK, BK, Cfg192>(a, batch, st);
+      if constexpr (AK) return launch_glds<OutT, AK, BK, Cfg192, true>(a, batch, st);
       else return launch_glds<OutT, AK, BK, Cfg128>(a, batch, st);
     case 12:
       if constexpr (AK) return launch_glds<OutT, AK, BK, Cfg192x256>(a, batch, st);
@@ -458,7 +528,7 @@ int launch_cfg(int cfg, const DenseArgs& a, int batch, hipStream_t st) {
       if constexpr (AK) return launch_glds<OutT, AK, BK, Cfg192w8>(a, batch, st);
       else return launch_glds<OutT, AK, BK, Cfg128>(a, batch, st);
     case 15:
-      if constexpr (AK) return launch_glds<OutT, AK, BK, Cfg192w8s3>(a, batch, st);
+      if constexpr (AK) return launch_glds<OutT, AK, BK, Cfg192w8s3, true>(a, batch, st);
       else return launch_glds<OutT, AK, BK, Cfg128>(a, batch, st);
     case 17:
       if constexpr (AK) return launch_glds<OutT, AK, BK, Cfg192w8s4>(a, batch, st);

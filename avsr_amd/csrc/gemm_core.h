@@ -407,9 +407,43 @@ template <typename T> AVSR_DEV void st8(T* p, const float (&o)[8]) {
   }
 }
 
-// epi_elems for 8 full columns [col, col+8) with 16-byte loads/stores (epi_vec_ok, col+8 <= N)
+// Compile-time epilogue variants of the LDS-DMA core's vector path (dense_glds_kernel): the host
+// classifies a launch (gemm.hip epi_variant) and the kernel pins the Epi fields the variant fixes
+// (epi_fold), so the tests of epi_vec8 / epilogue_g on them fold away and a wave runs straight-line
+// code. The arithmetic of every element is the generic path's: same operations, same order.
+//   EV_PLAIN         C = acc                                   (forward or backward)
+//   EV_BIAS          C = acc + bias
+//   EV_BIAS_RES      C = dropout(acc + bias) + res             (drop_p at run time, may be 0)
+//   EV_BIAS_ACT_PRE  preact = acc + bias; C = dropout(gelu(preact))
+//   EV_GATE          C = dropout_mask(acc) * gelu'(gate), optional column sums (backward)
+// all with alpha = 1, beta = 0, no atomics / statistics / row map, and every tile on the 8-column
+// vector path (N % 8 == 0, 16-byte aligned operands and strides).
+enum { EV_GENERIC = 0, EV_PLAIN = 1, EV_BIAS = 2, EV_BIAS_RES = 3, EV_BIAS_ACT_PRE = 4, EV_GATE = 5 };
+
+template <int EV> AVSR_DEV void epi_fold(Epi& e) {
+  if constexpr (EV != EV_GENERIC) {
+    e.alpha = 1.f; e.beta = 0.f; e.atomic = 0; e.stats = nullptr; e.rm_wc = 0;
+    e.bwd = EV == EV_GATE;
+    if constexpr (EV == EV_PLAIN || EV == EV_GATE) e.bias = nullptr;
+    else __builtin_assume(e.bias != nullptr);
+    if constexpr (EV == EV_BIAS_ACT_PRE) __builtin_assume(e.preact != nullptr);
+    else e.preact = nullptr;
+    if constexpr (EV == EV_BIAS_RES) __builtin_assume(e.res != nullptr);
+    else e.res = nullptr;
+    if constexpr (EV == EV_GATE) __builtin_assume(e.gate != nullptr);
+    else e.gate = nullptr;
+    e.act = (EV == EV_BIAS_ACT_PRE || EV == EV_GATE) ? AVSR_ACT_GELU : AVSR_ACT_NONE;
+    if constexpr (EV == EV_PLAIN || EV == EV_BIAS) e.drop_p = 0.f;
+    if constexpr (EV != EV_GATE) e.colsum = nullptr;
+  }
+}
+
+// epi_elems for 8 full columns [col, col+8) with 16-byte loads/stores (epi_vec_ok, col+8 <= N).
+// bv: the 8 bias values if the caller holds them already (a thread's column group is fixed);
+// op: the residual (forward) / gate (backward) vector if the caller has loaded it already.
 template <typename T, typename OutT>
-AVSR_DEV void epi_vec8(const Epi& e, int row, int col, float (&v)[8]) {
+AVSR_DEV void epi_vec8(const Epi& e, int row, int col, float (&v)[8], const float* bv = nullptr,
+                       const bf16x8* op = nullptr) {
   const int64_t off = (int64_t)row * e.ldc + col;
 #pragma unroll
   for (int q = 0; q < 8; ++q) v[q] *= e.alpha;
@@ -417,7 +451,12 @@ AVSR_DEV void epi_vec8(const Epi& e, int row, int col, float (&v)[8]) {
   const uint64_t d0 = e.drop_base + (uint64_t)row * (uint64_t)e.N + col;
   if (!e.bwd) {
     if (e.bias) {
-      ld8(e.bias + col, t);
+      if (bv) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = bv[q];
+      } else {
+        ld8(e.bias + col, t);
+      }
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] += t[q];
     }
@@ -436,14 +475,24 @@ AVSR_DEV void epi_vec8(const Epi& e, int row, int col, float (&v)[8]) {
     }
     if (e.drop_p > 0.f) drop8(e.drop_p, e.seed, d0, v);
     if (e.res) {
-      ld8((const T*)e.res + (int64_t)row * e.ldr + col, t);
+      if (op) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = (float)(*op)[q];
+      } else {
+        ld8((const T*)e.res + (int64_t)row * e.ldr + col, t);
+      }
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] += t[q];
     }
   } else {
     if (e.drop_p > 0.f) drop8(e.drop_p, e.seed, d0, v);
     if (e.gate) {
-      ld8((const T*)e.gate + off, t);
+      if (op) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) t[q] = (float)(*op)[q];
+      } else {
+        ld8((const T*)e.gate + off, t);
+      }
       if (sizeof(T) == 2 && e.act == AVSR_ACT_GELU) {
 #pragma unroll
         for (int q = 0; q < 8; q += 2) {

@@ -310,13 +310,16 @@ AVSR_DEV void mainloop_glds(const LA& la, const LB& lb, int kbeg, int nk, f32x4 
 // through LDS and writing it row-major, 8 consecutive columns per thread (one 16-byte store
 // per bf16 output row segment; 16-byte preact/residual/gate reads). Accumulator tile (ti, tj) register r sits at wave-local row
 // 16ti + 4(lane>>4) + r, column 16tj + (lane&15).
-template <typename T, typename OutT, class CF>
+// EV (gemm_core.h): a compile-time epilogue variant, `e` already pinned by epi_fold<EV>: every
+// vector of the tile takes the 8-column path, the thread's bias values are loaded once, and the
+// strip's residual / gate vectors are requested before the staging barriers.
+template <typename T, typename OutT, class CF, int EV = EV_GENERIC>
 AVSR_DEV void epilogue_g(const Epi& e, int m0, int n0, f32x4 (&acc)[CF::TM][CF::TN], char* smem) {
   constexpr int BN = CF::BN, LDR = BN + 4, SR = CF::WM * 32;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / CF::WN, wn = wave % CF::WN;
   float* st = (float*)smem;
-  const bool vec = epi_vec_ok<T, OutT>(e);
+  const bool vec = EV != EV_GENERIC || epi_vec_ok<T, OutT>(e);
   if (e.stats) {
     __syncthreads();
     float* red = st;  // [WM][BN][3]
@@ -375,8 +378,31 @@ AVSR_DEV void epilogue_g(const Epi& e, int m0, int n0, f32x4 (&acc)[CF::TM][CF::
   float cs[8];          // column sums of this thread's stored values (e.colsum)
 #pragma unroll
   for (int j = 0; j < 8; ++j) cs[j] = 0.f;
+  // variant path: the thread's column group (fixed, see the assertion) and row count per strip
+  constexpr int CGV = BN / 8, IT = SR * CGV / CF::NTH;
+  constexpr bool PREB = EV == EV_BIAS || EV == EV_BIAS_RES || EV == EV_BIAS_ACT_PRE;
+  constexpr bool PREOP = (EV == EV_BIAS_RES || EV == EV_GATE) && sizeof(T) == 2;
+  static_assert(EV == EV_GENERIC || IT * CF::NTH == SR * CGV, "whole vectors per thread per strip");
+  const int lc0 = (tid % CGV) * 8;
+  float bv[8];
+  if constexpr (PREB) {
+    if (n0 + lc0 < e.N) ld8(e.bias + n0 + lc0, bv);     // N % 8 == 0: the whole group is in range
+  }
 #pragma unroll
   for (int i = 0; i < CF::FM; ++i) {
+    bf16x8 pre[PREOP ? IT : 1];
+    if constexpr (PREOP) {
+#pragma unroll
+      for (int it = 0; it < IT; ++it) {
+        const int lr = (tid + it * CF::NTH) / CGV;
+        const int row = m0 + ((lr >> 5) * CF::FM + i) * 32 + (lr & 31);
+        if (row < e.M && n0 + lc0 < e.N) {
+          const int orow = epi_row(e, row);
+          pre[it] = EV == EV_GATE ? *(const bf16x8*)((const bf16*)e.gate + (int64_t)orow * e.ldc + n0 + lc0)
+                                  : *(const bf16x8*)((const bf16*)e.res + (int64_t)orow * e.ldr + n0 + lc0);
+        }
+      }
+    }
     __syncthreads();
 #pragma unroll
     for (int h = 0; h < 2; ++h)
@@ -388,6 +414,23 @@ AVSR_DEV void epilogue_g(const Epi& e, int m0, int n0, f32x4 (&acc)[CF::TM][CF::
           st[lr * LDR + (wn * CF::TN + j) * 16 + (lane & 15)] = acc[2 * i + h][j][r];
         }
     __syncthreads();
+    if constexpr (EV != EV_GENERIC) {
+#pragma unroll
+      for (int it = 0; it < IT; ++it) {
+        const int lr = (tid + it * CF::NTH) / CGV;
+        const int row = m0 + ((lr >> 5) * CF::FM + i) * 32 + (lr & 31);
+        const int col = n0 + lc0;
+        if (row < e.M && col < e.N) {
+          const f32x4 v0 = *(const f32x4*)(st + lr * LDR + lc0), v1 = *(const f32x4*)(st + lr * LDR + lc0 + 4);
+          float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+          epi_vec8<T, OutT>(e, epi_row(e, row), col, v, PREB ? bv : nullptr, PREOP ? &pre[it] : nullptr);
+          if (e.colsum) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) cs[j] += v[j];
+          }
+        }
+      }
+    } else
     for (int c = tid; c < SR * BN / 8; c += CF::NTH) {
       const int lr = c / (BN / 8), lc = (c % (BN / 8)) * 8;
       const int row = m0 + ((lr >> 5) * CF::FM + i) * 32 + (lr & 31);
