@@ -108,7 +108,7 @@ def prioritize_step_stream(device):
 def wgrad_splitk(M, N, K):
     """token-dimension split of a weight-gradient GEMM dW[N][K] += dy[M][N]^T x[M][K] over
     blocks. The library runs weight-gradients as 8-wave blocks that already split their K range
-    between two wave groups (gemm.hip wgrad_dual_kernel, one block per CU), so the block grid is
+    between two wave groups (gemm_wgrad.hip wgrad_dual_kernel, one block per CU), so the block grid is
     split only when the 128x128 tiles fill less than half the chip (out-proj 1024x1024: 64 tiles
     x 4), through a slab workspace (no atomics). With the library option wgrad_dual = 0 (A/B):
     the 4-wave core at two blocks per CU with its 512-block target."""

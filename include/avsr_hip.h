@@ -77,12 +77,15 @@ enum {
   AVSR_OPT_STEM_WPATCH = 9,
   AVSR_OPT_COUNT = 10
 };
-/* tile configurations of the bf16 GEMM core (AVSR_OPT_GEMM_TILE = k + 1) */
+/* tile configurations of the bf16 GEMM core (AVSR_OPT_GEMM_TILE = k + 1): rows x columns, wN =
+ * N waves, sN = N LDS stages, PP = the 256x256 ping-pong core. One row each in gemm.hip's tile
+ * table, one name each in avsr_amd/_lib.py TILES (tests/test_lib_abi.py compares them). The ids
+ * are not persistent (tools, tests and profiles use the names): measured-and-dropped
+ * configurations leave and the rest are renumbered. */
 enum {
   AVSR_TILE_128 = 0, AVSR_TILE_256 = 1, AVSR_TILE_256x128 = 2, AVSR_TILE_128x256 = 3, AVSR_TILE_128s3 = 4,
-  AVSR_TILE_128s4 = 5, AVSR_TILE_128w8s3 = 6, AVSR_TILE_128w8s4 = 7, AVSR_TILE_PP = 8, AVSR_TILE_96 = 9,
-  AVSR_TILE_128x64 = 10, AVSR_TILE_192 = 11, AVSR_TILE_192x256 = 12, AVSR_TILE_192s3 = 13, AVSR_TILE_192w8 = 14,
-  AVSR_TILE_192w8s3 = 15, AVSR_TILE_64 = 16, AVSR_TILE_192w8s4 = 17, AVSR_TILE_64s4 = 18, AVSR_TILE_COUNT = 19
+  AVSR_TILE_128w8s3 = 5, AVSR_TILE_PP = 6, AVSR_TILE_192 = 7, AVSR_TILE_192x256 = 8, AVSR_TILE_192w8s3 = 9,
+  AVSR_TILE_64 = 10, AVSR_TILE_64s4 = 11, AVSR_TILE_COUNT = 12
 };
 int avsr_set_option(int option, int64_t value);
 int64_t avsr_get_option(int option);

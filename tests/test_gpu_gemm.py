@@ -93,7 +93,7 @@ def _ref_gemm(A, B, a_kmajor, b_kmajor):
     return Af @ Bf.t()
 
 
-@pytest.fixture(params=["auto", "128", "256", "256x128", "128x256", "128s3", "128w8s3", "pp", "192", "192x256", "64"])
+@pytest.fixture(params=["auto"] + L.TILES)
 def gemm_tile(request, lib_opt):
     """forces each LDS-DMA tile configuration (library option gemm_tile, read per launch by avsr_gemm)"""
     lib_opt("gemm_tile", request.param)
@@ -228,7 +228,7 @@ def test_dgrad_fused_bias_grad(dev, gemm_tile, M, N, K):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("tile", ["192", "192x256", "256x128", "pp", "64", "64s4"])
+@pytest.mark.parametrize("tile", [t for t in L.TILES if t != "128"])
 def test_tile_configs_bit_identical(dev, monkeypatch, tile, lib_opt):
     """Every tile configuration accumulates each output over the same K order (64-deep K-tiles,
     the same 16x16x32 MFMA sequence), so the fused-epilogue results must equal the 128x128

@@ -80,6 +80,17 @@ def test_kernel_options_declared_and_defaulted():
     assert lib.avsr_get_option(count) == -1 and lib.avsr_get_option(-1) == -1
 
 
+def test_tile_names_match_header():
+    """the AVSR_TILE_* ids of avsr_hip.h are dense, and their names in id order are Python's
+    TILES (set_option turns a tile name into its id by position)"""
+    src = open(os.path.join(ROOT, "include", "avsr_hip.h")).read()
+    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"\bAVSR_TILE_([A-Za-z0-9]+)\s*=\s*(\d+)", src)}
+    count = ids.pop("COUNT")
+    assert sorted(ids.values()) == list(range(count))
+    assert [n.lower() for n in sorted(ids, key=ids.get)] == L.TILES
+    assert count == len(L.TILES)
+
+
 def test_set_option_roundtrip_and_range():
     lib = L.load()
     assert lib.avsr_set_option(L.OPTIONS["attn_sq_bwd"], 2) == 1004          # AVSR_E_ARG: out of range

@@ -1,5 +1,5 @@
 """bf16 GEMM cores on square and encoder shapes (random [-1,1) operands, HIP-graph timed):
-library option gemm_tile in {auto, 128, pp, 256}. usage: python tools/gemm_sq.py [cfg,cfg,...]"""
+library option gemm_tile = auto or a name of avsr_amd._lib.TILES (default 128, pp, 256). usage: python tools/gemm_sq.py [cfg,cfg,...]"""
 import os
 import sys
 
