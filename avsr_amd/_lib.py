@@ -137,6 +137,14 @@ class CtcParams(ctypes.Structure):
     ]
 
 
+class CtcAlignParams(ctypes.Structure):
+    _fields_ = [
+        ("dtype", _i), ("B", _i), ("T", _i), ("V", _i), ("Lmax", _i), ("blank", _i), ("x", _c_p), ("ldx", _i64),
+        ("lse", _c_p), ("labels", _c_p), ("label_len", _c_p), ("in_len", _c_p),
+        ("ws", _c_p), ("ali", _c_p), ("score", _c_p), ("feasible", _c_p),
+    ]
+
+
 class EwParams(ctypes.Structure):
     _fields_ = [
         ("dtype", _i), ("rows", _i), ("N", _i), ("dy", _c_p), ("lddy", _i64), ("out", _c_p), ("ldout", _i64),
@@ -279,6 +287,7 @@ SYMBOLS = {
     "avsr_lsm_bwd": ([ctypes.POINTER(XentParams), _c_p], _i),
     "avsr_ctc_fwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_bwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
+    "avsr_ctc_align": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
     "avsr_loss_finalize": ([_i, _c_p, _i, _c_p, _c_p, _f, _i, _c_p, _c_p], _i),
     "avsr_ew_bwd": ([ctypes.POINTER(EwParams), _c_p], _i),
     "avsr_colsum_defer": ([_i], _i),

@@ -268,6 +268,14 @@ class CTCHead(_Holder):
         from ..surface import ctc_argmax
         return ctc_argmax(_e2e(self), hs_pad)
 
+    def forced_align(self, h, y, blank_id=0):
+        from ..surface import ctc_forced_align
+        return ctc_forced_align(_e2e(self), h, y, blank_id)
+
+    def forced_align_batch(self, hs_pad, ys_pad, ilens, blank_id=0):
+        from ..surface import ctc_forced_align_batch
+        return ctc_forced_align_batch(_e2e(self), hs_pad, ys_pad, ilens, blank_id)
+
 
 CTC = CTCHead
 

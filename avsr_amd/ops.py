@@ -658,6 +658,31 @@ def ctc_bwd(p, dloss, coef, dx):
     return dx
 
 
+def ctc_align_ws(B, T, Lmax):
+    """bytes of back-pointer workspace of ctc_align (AVSR_CTC_ALIGN_WS)"""
+    return (B * T * (2 * Lmax + 1) + 3) & ~3
+
+
+def ctc_align(x, B, T, V, labels, label_len, in_len, lse, *, blank=0, ali=None, score=None, feasible=None, ws=None):
+    """CTC forced alignment (avsr_ctc_align) of B utterances over logits x (rows b*T + t, fp32 or
+    bf16) with row log-sum-exp lse: fills / returns ali (B, T) int32 (-1 beyond in_len and on
+    infeasible rows), score (B,) fp32 and feasible (B,) int32. labels (B, Lmax) int32."""
+    dev = x.device
+    Lmax = labels.shape[1]
+    if ali is None:
+        ali = torch.empty(B, T, device=dev, dtype=torch.int32)
+    if score is None:
+        score = torch.empty(B, device=dev, dtype=torch.float32)
+    if feasible is None:
+        feasible = torch.empty(B, device=dev, dtype=torch.int32)
+    if ws is None and 2 * Lmax + 1 <= 1024:      # beyond the bound the launcher returns the shape error
+        ws = torch.empty(max(4, ctc_align_ws(B, T, Lmax)), device=dev, dtype=torch.uint8)
+    _call("avsr_ctc_align", L.fill(L.CtcAlignParams, dtype=dtype_code(x), B=B, T=T, V=V, Lmax=Lmax, blank=blank,
+                                    x=x, ldx=x.stride(0), lse=lse, labels=labels, label_len=label_len,
+                                    in_len=in_len, ws=ws, ali=ali, score=score, feasible=feasible))
+    return ali, score, feasible
+
+
 def loss_finalize(B, nll, row_loss, row_correct, mtlalpha, out, att_per_token=False):
     """att_per_token: the attention loss divides by the number of target tokens
     (transformer_length_normalized_loss) instead of B"""

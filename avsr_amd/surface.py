@@ -7,8 +7,8 @@ Callers of the reference reach the model through three sub-modules of `AVHubertA
         src/nets/backend/backbones/avhubert.py:546-561
   decoder.forward / forward_one_step / score / batch_score
         src/nets/backend/transformer/decoder.py:122-227
-  ctc.forward / log_softmax / softmax / argmax
-        src/nets/backend/ctc.py:83-180
+  ctc.forward / log_softmax / softmax / argmax / forced_align / forced_align_batch
+        src/nets/backend/ctc.py:83-328
 
 The functions here implement those entry points on an `Engine` (avsr_amd.engine); the
 parameter-holder modules of avsr_amd.nets.modules forward to them. Semantics follow the
@@ -298,3 +298,64 @@ def ctc_forward(e2e, hs_pad, hlens, ys_pad):
     for b in range(B):                      # (B*T, V) rows -> (T, B, V) like ys_hat.transpose(0, 1)
         ops.cast(logits[b * T:(b + 1) * T, :eng.V], ys_hat[:, b, :])
     return out4[1], ys_hat
+
+
+def _aligned_or_raise(ali, feas, ilens, what):
+    bad = [b for b in range(len(feas)) if not feas[b]]
+    if bad:
+        raise ValueError(f"{what}: no CTC alignment exists for utterance(s) {bad} "
+                         "(fewer frames than labels + adjacent repeated labels, or no frames)")
+    return [ali[b, :int(ilens[b])].astype("int64") for b in range(len(feas))]
+
+
+@torch.no_grad()
+def ctc_forced_align_batch(e2e, hs_pad, ys_pad, ilens, blank_id=0):
+    """CTC.forced_align_batch (ctc.py:246-328): hs_pad (T, B, V) LOGITS (the reference applies
+    log_softmax to them directly, it does not call ctc_lo here), ys_pad (B, L) padded with
+    ignore_id = -1, ilens (B,) -> list of B int64 numpy arrays, the token id of the best path
+    at each of the ilens[b] frames. The Viterbi runs on the device (avsr_ctc_align). Where the
+    reference backtracks through unset pointers and returns garbage (no alignment exists:
+    ilens[b] < labels + adjacent repeats), this raises ValueError naming the utterances."""
+    from .align import _align_logits
+    eng = e2e.engine()
+    T, B, V = hs_pad.shape
+    if V != eng.V:
+        raise ValueError(f"forced_align_batch takes (T, B, {eng.V}) logits, got last dim {V}")
+    if B == 0:
+        return []
+    if T == 0:
+        raise ValueError("forced_align_batch: no frames")
+    hs = to_engine(eng, hs_pad.detach(), torch.float32)
+    logits = torch.zeros(B * T, eng.Vp, device=eng.device, dtype=torch.float32)
+    for b in range(B):                      # (T, B, V) -> rows b*T + t
+        ops.cast(hs[:, b, :], logits[b * T:(b + 1) * T, :V])
+    lab = torch.as_tensor(ys_pad).detach().cpu()
+    ys = [r[r != -1].tolist() for r in lab]
+    il = [int(t) for t in torch.as_tensor(ilens).detach().cpu().reshape(-1)]
+    ali, _, feas = _align_logits(eng, logits, B, T, ys, il, blank_id)
+    return _aligned_or_raise(ali, feas, il, "forced_align_batch")
+
+
+@torch.no_grad()
+def ctc_forced_align(e2e, h, y, blank_id=0):
+    """CTC.forced_align (ctc.py:181-244): h hidden states (T, D) or (1, T, D), through ctc_lo
+    on the engine as in ctc_log_softmax; y the label ids -> list of T ints.
+
+    Defined as the batch form on one utterance. The reference's own single-utterance loop is
+    NOT reproduced: at state s = 0 it reads candidate logdelta[t-1, s-1] with s - 1 = -1,
+    which numpy wraps to the LAST state, so with any slack the path re-enters state 0 from the
+    final blank and emits the label sequence a second time (not an alignment of y); it agrees
+    with forced_align_batch only where no slack lets the wrap win. Raises ValueError when no
+    alignment exists."""
+    from .align import _align_logits
+    eng = e2e.engine()
+    if h.dim() == 2:
+        h = h.unsqueeze(0)
+    if h.dim() != 3 or h.shape[0] != 1:
+        raise ValueError(f"forced_align takes (T, D) or (1, T, D) hidden states, got {tuple(h.shape)}")
+    T = h.shape[1]
+    if T == 0:
+        raise ValueError("forced_align: no frames")
+    ys = [[int(t) for t in torch.as_tensor(y).reshape(-1).tolist()]]
+    ali, _, feas = _align_logits(eng, _ctc_logits(eng, h), 1, T, ys, [T], blank_id)
+    return _aligned_or_raise(ali, feas, [T], "forced_align")[0].tolist()

@@ -486,6 +486,40 @@ int avsr_loss_finalize(int B, const float* nll, int rows, const float* row_loss,
                        float mtlalpha, int att_per_token, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * avsr_ctc_align: CTC forced alignment, the best (Viterbi) path of CTC.forced_align_batch
+ *   (ctc.py:246-328) for B utterances in one launch, on raw logits x (rows b*T + t) and their
+ *   row log-sum-exp. Over the extended sequence ext = blank, y1, blank, ..., yL, blank
+ *   (S = 2L + 1 states), in fp32, with e(t, s) = float(x[t][ext_s]) - lse[t]:
+ *     d[0][0] = e(0, 0), d[0][1] = e(0, 1), every other state unreachable (-inf)
+ *     d[t][s] = max(c0, c1, c2) + e(t, s),  c0 = d[t-1][s],  c1 = d[t-1][s-1] (s >= 1),
+ *               c2 = d[t-1][s-2] (s >= 2, ext_s != blank, ext_s != ext_{s-2})
+ *   back-pointer = the FIRST maximum in the order (s, s-1, s-2); the final state is the first
+ *   maximum of (S-2, S-1) (state 0 for L = 0) at t = in_len[b] - 1, as in the reference. Every
+ *   rounding and tie is fixed, so a float32 host Viterbi reproduces ali and score bit for bit.
+ *   ali[b][t] = token of the best path (-1 at t >= in_len[b]); score[b] = its log-probability;
+ *   feasible[b] = 0 with ali[b][:] = -1 and score[b] = 0 when in_len[b] <= 0, when no path
+ *   exists (in_len[b] < L + number of adjacent equal labels; the reference returns garbage
+ *   there) or when a label is outside [0, V). Other utterances of the launch are unaffected.
+ *   ws: caller-owned back-pointers, AVSR_CTC_ALIGN_WS(B, T, Lmax) BYTES (one byte per
+ *   (b, t, state), rounded up to whole dwords; 4-byte aligned, AVSR_E_ALIGN otherwise);
+ *   contents on entry are irrelevant. Label-length bound as avsr_ctc_fwd:
+ *   2*Lmax + 1 <= 1024 (AVSR_E_SHAPE beyond it); T is not bounded. No allocation, no sync.
+ * ------------------------------------------------------------------------------------ */
+typedef struct {
+  int dtype, B, T, V, Lmax, blank;     /* dtype of x: AVSR_F32 or AVSR_BF16 */
+  const void* x; int64_t ldx;          /* logits, rows b*T + t, V valid columns */
+  const float* lse;                    /* [B*T] */
+  const int* labels;                   /* [B][Lmax] */
+  const int* label_len; const int* in_len;   /* [B] */
+  unsigned char* ws;                   /* AVSR_CTC_ALIGN_WS(B, T, Lmax) bytes */
+  int* ali;                            /* [B][T] */
+  float* score;                        /* [B] */
+  int* feasible;                       /* [B] */
+} avsr_ctc_align_params;
+#define AVSR_CTC_ALIGN_WS(B, T, Lmax) (((int64_t)(B) * (T) * (2 * (int64_t)(Lmax) + 1) + 3) & ~(int64_t)3)
+int avsr_ctc_align(const avsr_ctc_align_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Elementwise / data-movement kernels around the GEMMs.
  * avsr_ew_bwd:     out = alpha * dy * dropmask(drop_p, seed; idx = row*N + col) * act'(gate),
  *                  db[n] += sum_rows out  (bias gradients of the Linear layers; out optional)
