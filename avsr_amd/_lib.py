@@ -282,6 +282,7 @@ SYMBOLS = {
     "avsr_attn_bwd_prep": ([ctypes.POINTER(AttnParams), _c_p], _i),
     "avsr_attn_bwd": ([ctypes.POINTER(AttnParams), _c_p], _i),
     "avsr_attn_dropmask": ([ctypes.POINTER(AttnParams), _c_p], _i),
+    "avsr_attn_path": ([ctypes.POINTER(AttnParams), _i], _i),
     "avsr_row_lse": ([ctypes.POINTER(XentParams), _c_p], _i),
     "avsr_lsm_fwd": ([ctypes.POINTER(XentParams), _c_p], _i),
     "avsr_lsm_bwd": ([ctypes.POINTER(XentParams), _c_p], _i),
@@ -362,6 +363,7 @@ OPTIONS = {"gemm_tile": 0, "attn_sq_fwd": 1, "attn_sq_bwd": 2, "wgrad_dual": 3, 
            "conv_patch": 6, "conv_wpatch": 7, "stem_pool_2x2": 8,
            "stem_wpatch": 9}
 TILES = ["128", "256", "256x128", "128x256", "128s3", "128w8s3", "pp", "192", "192x256", "192w8s3", "64", "64s4"]
+ATTN_PATHS = ["f32", "tiled", "resident", "sq", "enc"]      # AVSR_ATTN_PATH_* in id order (avsr_attn_path)
 
 
 def set_option(name, value):

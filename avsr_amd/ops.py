@@ -563,6 +563,19 @@ def _attn_params(q, k, v, o, B, H, Lq, Lk, lse, klen, causal, scale, drop_p, see
                   lse=lse, klen=klen, causal=int(causal), drop_p=float(drop_p), seed=int(seed) & (2 ** 64 - 1))
 
 
+def attn_path(dtype, B, H, Lq, Lk, *, causal=False, backward=False, ld=None, lddo=None):
+    """avsr_attn_path: the kernel family (a name of _lib.ATTN_PATHS) that attn_fwd, or with backward
+    attn_bwd, runs for this shape under the current options; host-only, no tensors. dtype: a torch
+    dtype or an AVSR_* code; ld: the row stride of q / k / v / o (default H * 64); lddo: of dout."""
+    ld = H * 64 if ld is None else ld
+    p = L.fill(L.AttnParams, dtype=_DT.get(dtype, dtype), B=B, H=H, Lq=Lq, Lk=Lk, causal=int(causal), ldq=ld, ldk=ld,
+               ldv=ld, ldo=ld, lddo=H * 64 if lddo is None else lddo)
+    rc = L.load().avsr_attn_path(ctypes.byref(p), int(backward))
+    if not 0 <= rc < len(L.ATTN_PATHS):
+        L.check(rc, "avsr_attn_path")
+    return L.ATTN_PATHS[rc]
+
+
 def attn_mask_words(B, H, Lq, Lk):
     """AVSR_ATTN_MASK_WORDS: 64-bit words of one attention call's stored dropout keep mask"""
     return B * H * ((Lq + 31) // 32) * (2 * ((Lk + 63) // 64)) * 16

@@ -375,8 +375,18 @@ int avsr_avgpool_bwd(int dtype, int nimg, int P, int C, const void* dy, void* dx
  *   j <= i.  Optional dropout on the probabilities (counter-based; bwd recomputes it).
  * fwd stores lse[b][h][i] (natural log) for the backward.
  * bwd: dq (fp32 accumulator [B*Lq][ldq_f32], atomics, caller zeroes) or dq_out (dtype),
- *   dk, dv (dtype); needs delta[b][h][i] = sum_d dO*O from avsr_attn_bwd_prep. bf16 runs
- *   two streaming kernels (dK/dV per key block, dQ per query block), fp32 one atomic kernel.
+ *   dk, dv (dtype); call avsr_attn_bwd_prep first (delta[b][h][i] = sum_d dO*O where the
+ *   backward kernels do not compute it themselves).
+ * Five kernel families (AVSR_ATTN_PATH_*; avsr_attn_path tells which one a call runs):
+ *   F32       fp32 storage: one forward kernel, one backward kernel (dQ by atomics)
+ *   TILED     bf16, any shape: 64-row tiles streamed through LDS; dK/dV per key block, dQ per
+ *             query block, no atomics
+ *   RESIDENT  bf16, the streamed operands of a whole head resident in LDS: forward Lk <= 384,
+ *             backward Lq and Lk <= 384 (the decoder's self / source attention)
+ *   SQ        bf16 forward, non-causal, Lq >= 128: query-tiled, K / V through an LDS-DMA ring
+ *             (the encoder's self-attention; with AVSR_OPT_ATTN_SQ_FWD off: RESIDENT / TILED instead)
+ *   ENC       bf16 backward, non-causal, 128 <= Lq, Lk <= 384, lddo % 8 == 0 (its backward)
+ *   SQ, RESIDENT and ENC also need B*H*Lq*ceil(Lk/2) < 2^32; other bf16 calls run TILED.
  * Replaces: HF:eager_attention_forward + Wav2Vec2Attention core (:438-548; encoder, key
  *   padding mask from avhubert.py:688-696) and MultiHeadedAttention.forward_attention
  *   (src/nets/backend/transformer/attention.py:56-106; decoder causal self-attention and
@@ -406,8 +416,8 @@ typedef struct {
    * (s = 0), dK (s = 1), dV (s = 2) values as stored (bf16-rounded in bf16) — the fused q/k/v
    * projection bias gradients. db_ws: AVSR_ATTN_DB_WS(B, H) floats of per-utterance partials,
    * finalised through the column-sum path (deferred like avsr_gemm db: keep it alive until the
-   * flush). The resident bf16 kernels sum them in their store epilogues; other paths run one
-   * extra pass over dq/dk/dv. NULL: off. */
+   * flush). Every path computes them in one extra pass over the stored dq/dk/dv after the
+   * backward kernels. NULL: off. */
   float* db; float* db_ws;
   /* optional probability-dropout keep mask (bf16, non-causal): written once per (seed, shape)
    * by avsr_attn_dropmask, then read by avsr_attn_fwd / avsr_attn_bwd in place of re-hashing
@@ -430,6 +440,16 @@ int avsr_debug_attn_stamps(unsigned long long* buf);
 int avsr_attn_fwd(const avsr_attn_params* p, void* stream);
 int avsr_attn_bwd_prep(const avsr_attn_params* p, void* stream);   /* delta = rowsum(dO * O) */
 int avsr_attn_bwd(const avsr_attn_params* p, void* stream);
+/* the kernel family avsr_attn_fwd (pass = AVSR_ATTN_FWD) or avsr_attn_bwd_prep / avsr_attn_bwd
+ * (AVSR_ATTN_BWD) run for this call under the current options: an AVSR_ATTN_PATH_* id, or the
+ * AVSR_E_* code those calls return for it. Host-only: reads the struct's integers, dereferences
+ * no pointer and touches no device. */
+enum { AVSR_ATTN_FWD = 0, AVSR_ATTN_BWD = 1 };
+enum {
+  AVSR_ATTN_PATH_F32 = 0, AVSR_ATTN_PATH_TILED = 1, AVSR_ATTN_PATH_RESIDENT = 2, AVSR_ATTN_PATH_SQ = 3,
+  AVSR_ATTN_PATH_ENC = 4
+};
+int avsr_attn_path(const avsr_attn_params* p, int pass);
 /* fills p->drop_mask (AVSR_ATTN_MASK_WORDS words) with the keep decisions of drop_p / seed for
  * (B, H, Lq, Lk): the data-independent half of the attention dropout, runnable ahead of the
  * forward on another stream. Same replacement as avsr_attn_fwd (the dropout of

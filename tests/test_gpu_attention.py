@@ -34,20 +34,29 @@ def _ref(q, k, v, B, H, Lq, Lk, klen, causal, scale, mask_mult=None):
 
 
 CASES = [
-    # B, H, Lq, Lk, klen, causal
-    (3, 4, 75, 75, [75, 60, 33], False),
-    (2, 2, 41, 41, None, True),
-    (3, 2, 41, 150, [150, 77, 129], False),
-    (2, 16, 375, 375, [375, 301], False),
-    (1, 2, 520, 520, [517], False),          # Lk > 384: streamed kernels only
-    (2, 3, 200, 130, [130, 65], False),      # cross-shaped, two q-blocks, the last one partial
+    # B, H, Lq, Lk, klen, causal, the kernel families (forward, backward) the bf16 run is there for
+    (3, 4, 75, 75, [75, 60, 33], False, ("resident", "resident")),
+    (2, 2, 41, 41, None, True, ("resident", "resident")),
+    (3, 2, 41, 150, [150, 77, 129], False, ("resident", "resident")),
+    (2, 16, 375, 375, [375, 301], False, ("sq", "enc")),
+    (1, 2, 520, 520, [517], False, ("sq", "tiled")),            # Lk > 384: query-tiled forward, tiled backward
+    (2, 3, 200, 130, [130, 65], False, ("sq", "enc")),          # cross-shaped, two q-blocks, the last one partial
+    (1, 2, 41, 400, [391], False, ("tiled", "tiled")),          # partial last key tile, klen inside it
+    (1, 1, 400, 400, None, True, ("tiled", "tiled")),           # causal over four 128-row blocks (fp32 too)
 ]
+
+
+def _assert_paths(dtype, B, H, Lq, Lk, causal, paths):
+    """the call runs the kernel family the case is there for (fp32: always the parity kernels)"""
+    got = tuple(ops.attn_path(dtype, B, H, Lq, Lk, causal=causal, backward=bwd) for bwd in (False, True))
+    assert got == (paths if dtype == torch.bfloat16 else ("f32", "f32")), got
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("case", CASES)
 def test_attention(dev, dtype, case):
-    B, H, Lq, Lk, klen, causal = case
+    B, H, Lq, Lk, klen, causal, paths = case
+    _assert_paths(dtype, B, H, Lq, Lk, causal, paths)
     D = H * 64
     g = torch.Generator().manual_seed(B * 1000 + Lq)
     qkv = torch.randn(B * Lq, 3 * D, generator=g)          # fused layout [q | k | v]
@@ -135,11 +144,14 @@ def test_attention_dropout(dev):
     assert _rel(dv, vr.grad) < 1e-4
 
 
-def test_attention_dropout_bf16(dev):
-    """bf16 streaming kernels with probability dropout: the mask (same counter hash as the
+@pytest.mark.parametrize("L", [150, 400])
+def test_attention_dropout_bf16(dev, L):
+    """bf16 kernels with probability dropout (L = 150: query-tiled forward, encoder backward;
+    L = 400: query-tiled forward, tiled backward): the mask (same counter hash as the
     fp32 kernels) is recovered through one-hot V rows in fp32, then the bf16 fwd / bwd
     (dK, dV and both dQ outputs) are checked against the reference with that mask."""
-    B, H, L, p, seed = 2, 2, 150, 0.1, 4242
+    B, H, p, seed = 2, 2, 0.1, 4242
+    _assert_paths(torch.bfloat16, B, H, L, L, False, ("sq", "enc" if L <= 384 else "tiled"))
     D = H * 64
     g = torch.Generator().manual_seed(2)
     q = torch.randn(B * L, D, generator=g); k = torch.randn(B * L, D, generator=g)
@@ -344,7 +356,8 @@ def test_attention_bias_grad(dev, dtype, case):
     """avsr_attn_params.db: += the column sums of the dQ | dK | dV the backward stores (the fused
     q/k/v bias gradients, one pass over the outputs after the backward kernels) — against fp64
     sums of the stored tensors, dropout on"""
-    B, H, Lq, Lk, klen, causal = case
+    B, H, Lq, Lk, klen, causal, paths = case
+    _assert_paths(dtype, B, H, Lq, Lk, causal, paths)
     D = H * 64
     g = torch.Generator().manual_seed(B * 7 + Lk)
     q = torch.randn(B * Lq, D, generator=g).to(dev, dtype)
@@ -377,7 +390,7 @@ def test_attention_bias_grad(dev, dtype, case):
 
 # ---------------------------------------------------------------------------------------------
 # Stored dropout keep masks (avsr_attn_dropmask): the layout of include/avsr_hip.h against a
-# numpy restatement of the attention dropout's counter hash (AttnDrop, attention.hip: pair index
+# numpy restatement of the attention dropout's counter hash (AttnDrop, attention.h: pair index
 # g = ((b*H + h) * Lq + q) * ceil(Lk / 2) + k / 2, fmix32(g * 0x9E3779B1 ^ pre), 16-bit half by
 # key parity, kept iff >= round(p * 65536)); and kernel outputs with the stored mask == hashed.
 # ---------------------------------------------------------------------------------------------

@@ -59,6 +59,58 @@ def test_conv_stat_tiles_per_dtype():
     assert ops.conv_stat_tiles(g3, L.AVSR_BF16) == ops.conv_stat_tiles(g3, L.AVSR_F32) == -(-6000 * 484 // 256)
 
 
+_BIG = (64, 16, 4096, 4096)      # B*H*Lq*ceil(Lk/2) > 2^32 - 1: the dropout pair index needs 64 bits
+ATTN_PATH_TABLE = [
+    # (B, H, Lq, Lk), keywords of ops.attn_path, forward path, backward path; bf16 unless the keywords say otherwise
+    ((2, 2, 41, 41), dict(causal=True), "resident", "resident"),
+    ((3, 2, 41, 150), {}, "resident", "resident"),
+    ((2, 3, 200, 130), {}, "sq", "enc"),
+    ((1, 2, 127, 127), {}, "resident", "resident"),
+    ((1, 2, 128, 128), {}, "sq", "enc"),
+    ((1, 2, 128, 127), {}, "sq", "resident"),
+    ((1, 2, 384, 384), {}, "sq", "enc"),
+    ((1, 2, 385, 385), {}, "sq", "tiled"),
+    ((1, 2, 41, 385), {}, "tiled", "tiled"),
+    ((1, 2, 385, 41), {}, "sq", "tiled"),
+    ((1, 2, 200, 200), dict(causal=True), "resident", "resident"),
+    ((1, 1, 400, 400), dict(causal=True), "tiled", "tiled"),
+    ((1, 2, 200, 200), dict(lddo=2 * 64 + 4), None, "resident"),
+    (_BIG, {}, "tiled", "tiled"),
+    ((1, 2, 200, 200), dict(sq=0), "resident", "enc"),
+    ((1, 2, 520, 520), dict(sq=0), "tiled", "tiled"),
+    ((2, 2, 41, 41), dict(dtype=L.AVSR_F32), "f32", "f32"),
+    ((1, 2, 520, 520), dict(dtype=L.AVSR_F32), "f32", "f32"),
+]
+
+
+def test_attn_path_table():
+    """avsr_attn_path: which kernel family a shape runs, forward and backward, at every threshold
+    of the choice (128 and 384 rows, causal, the 32-bit dropout index, lddo alignment, the
+    attn_sq_fwd option, fp32); and the codes of a rejected call. Host-side query, no GPU."""
+    import pytest
+    import torch
+    from avsr_amd import ops
+    assert _BIG[0] * _BIG[1] * _BIG[2] * ((_BIG[3] + 1) // 2) > 0xFFFFFFFF
+    for shape, kw, fwd, bwd in ATTN_PATH_TABLE:
+        kw = dict(kw)
+        dtype = kw.pop("dtype", torch.bfloat16)
+        prev = L.set_option("attn_sq_fwd", kw.pop("sq", 1))
+        try:
+            if fwd is not None:
+                assert ops.attn_path(dtype, *shape, **kw) == fwd, (shape, kw, "fwd")
+            assert ops.attn_path(dtype, *shape, backward=True, **kw) == bwd, (shape, kw, "bwd")
+        finally:
+            L.set_option("attn_sq_fwd", prev)
+    assert L.get_option("attn_sq_fwd") == 1
+    with pytest.raises(L.AvsrLibError, match="1003"):                       # AVSR_E_DTYPE
+        ops.attn_path(7, 2, 2, 41, 41)
+    with pytest.raises(L.AvsrLibError, match="1002"):                       # AVSR_E_ALIGN
+        ops.attn_path(torch.bfloat16, 1, 2, 200, 200, ld=132)
+    p = L.fill(L.AttnParams, dtype=L.AVSR_BF16, B=1, H=2, Lq=200, Lk=200, ldq=128, ldk=128, ldv=128, ldo=128)
+    assert L.load().avsr_attn_path(ctypes.byref(p), 2) == 1004              # AVSR_E_ARG: no such pass
+    assert L.load().avsr_attn_path(None, 0) == 1004
+
+
 def _header_option_defaults():
     """{AVSR_OPT_name: default} from the bracketed defaults in avsr_hip.h's option table"""
     src = open(os.path.join(ROOT, "include", "avsr_hip.h")).read()
