@@ -27,6 +27,24 @@ def _round(n, a=ALIGN):
     return (n + a - 1) // a * a
 
 
+_NONE = frozenset()
+
+
+class Trainable:
+    """Which parameters a training forward found trainable (requires_grad, torch's rule): the
+    forward keeps it in its context and its backward follows it, whatever the flags say by then.
+    One object per distinct flag vector (Arena.snapshot caches them), so identity comparisons and
+    attributes hung on it (Engine._plan) stay valid from step to step.
+      all / any: every / some parameter trainable; frozen: frozenset of the frozen names."""
+    __slots__ = ("all", "any", "frozen", "plan")
+
+    def __init__(self, frozen, n):
+        self.frozen = frozen
+        self.all = not frozen
+        self.any = len(frozen) < n
+        self.plan = None
+
+
 class Arena:
     def __init__(self, root: nn.Module, device, compute_dtype=torch.bfloat16, fuse_groups=(), pad_rows=None,
                  perms=None, frozen=(), no_decay=None):
@@ -115,6 +133,18 @@ class Arena:
         # them as torch.optim.AdamW skips parameters whose grad is None)
         self.ld_ranges = None
         self.ld_touched = set()
+        # requires_grad=False (Trainable): _dead = the names frozen in EVERY backward since the last
+        # gradient clear (None: no backward yet) — they have no gradient, so nothing reads, sums,
+        # exchanges or applies their ranges; _dirty = frozen names whose ranges a fused epilogue
+        # (bias sums of a data-grad GEMM, the LayerNorm / BatchNorm backward) may have written
+        # anyway: zeroed before such a parameter has a gradient again
+        self._gnames = list(self.grad_views)
+        self._gparams = [self.params[n] for n in self._gnames]
+        self._snaps = {}
+        self.also_frozen = ()
+        self._nranges = {}
+        self._dead = None
+        self._dirty = set()
         self.update_event = None     # an overlapped optimizer update in flight (wait_update)
         self.grads_cleared = False   # that update also zeroed the gradients (Engine.zero_grad_async)
         self.attach_grads(zero=False)
@@ -205,23 +235,132 @@ class Arena:
         if self.data._version != self._synced_version:
             self.sync_shadow()
 
-    def attach_grads(self, zero=True):
+    # ------------------------------------------------------------------ requires_grad
+    def snapshot(self):
+        """the Trainable of the parameters' requires_grad flags as they are now (self.also_frozen:
+        name prefixes frozen whatever their flags; the engine's feature_grad_mult = 0). The flags
+        are read in one pass (torch gives no notice of a change; tens of microseconds of host time
+        for 699 tensors, beside a host that runs tens of ms ahead of the GPU); everything derived
+        from them — frozen names, ranges, the engine's plan, the optimizer's pieces — is cached per
+        flag vector, so an unchanged set costs that pass and a dict lookup."""
+        also_frozen = self.also_frozen
+        key = (bytes([p.requires_grad for p in self._gparams]), also_frozen)
+        snap = self._snaps.get(key)
+        if snap is None:
+            fz = [n for n, p in zip(self._gnames, self._gparams)
+                  if not p.requires_grad or (also_frozen and n.startswith(also_frozen))]
+            snap = self._snaps[key] = Trainable(frozenset(fz) if fz else _NONE, len(self._gnames))
+        return snap
+
+    def name_ranges(self, names):
+        """merged [start, end) arena ranges of the named parameters (a frozenset), each run out over
+        the alignment gap behind it (the gaps hold zeros and belong to nobody), so neighbours merge"""
+        r = self._nranges.get(names)
+        if r is None:
+            r = []
+            for s, e in sorted((self.meta[n]["off"], _round(self.meta[n]["off"] + self.meta[n]["numel"])) for n in names):
+                if r and s <= r[-1][1]:
+                    r[-1] = (r[-1][0], max(r[-1][1], e))
+                else:
+                    r.append((s, e))
+            self._nranges[names] = r
+        return r
+
+    def begin_backward(self, snap, dirty=_NONE):
+        """a backward under `snap` is about to write gradients: record which ranges it leaves
+        without one, zero the leftovers of earlier frozen steps in ranges that get one now, and
+        note the frozen ranges its fused epilogues may write (dirty). With nothing frozen and
+        nothing left over this is two assignments."""
+        self.grads_cleared = False
+        fz = _NONE if snap is None else snap.frozen
+        if self._dirty:
+            stale = self._dirty - fz
+            if stale:
+                for s, e in self.name_ranges(frozenset(stale)):
+                    self.grad[s:e].zero_()
+                self._dirty -= stale
+        if self._dead is None or not fz:
+            self._dead = fz
+        elif self._dead is not fz:
+            self._dead = self._dead & fz
+        if dirty:
+            self._dirty |= dirty
+
+    def dead_names(self):
+        """names no backward since the last gradient clear gave a gradient (frozen in all of them)"""
+        return self._dead or _NONE
+
+    def dead_ranges(self):
+        return self.name_ranges(self._dead) if self._dead else []
+
+    def written_ranges(self):
+        """[start, end) ranges a backward since the last clear may have written a gradient into
+        (None: the whole arena) — what a data-parallel exchange has to carry"""
+        dead = self.dead_ranges()
+        if not dead:
+            return None
+        out, pos = [], 0
+        for s, e in dead:
+            if pos < s:
+                out.append((pos, s))
+            pos = e
+        if pos < self.total:
+            out.append((pos, self.total))
+        return out
+
+    def zero_dirty(self):
+        """zero what fused epilogues left in frozen ranges (current stream): for a gradient clear
+        that otherwise only covers what the optimizer read (FusedAdamW clear_in_update)"""
+        if self._dirty:
+            for s, e in self.name_ranges(frozenset(self._dirty)):
+                self.grad[s:e].zero_()
+            self._dirty.clear()
+
+    def cleared(self, everything=True):
+        """bookkeeping of a gradient clear (everything: the whole buffer was zeroed)"""
+        self._dead = None
+        if everything:
+            self._dirty.clear()
+        self.ld_touched.clear()
+
+    def attach_grads(self, zero=True, snap=None):
         """(re)attach the gradient-arena views as .grad. A per-parameter optimizer's
         zero_grad(set_to_none=True) (HF Trainer, torch.optim) sets .grad to None: those
         parameters' gradients restart from zero, so their arena slices are cleared first (one
-        memset when every parameter was reset)."""
+        memset when every parameter was reset). A parameter frozen in `snap` (default: by its
+        flag now) has no gradient: its .grad is None."""
+        snap = snap or self.snapshot()
+        if not snap.all:
+            return self._attach_some(zero, snap.frozen)
         missing = [n for n, v in self.grad_views.items() if self.params[n].grad is not v]
         if not missing:
             return
         if zero:
             if len(missing) == len(self.grad_views):
                 self.grad.zero_()
+                self._dirty.clear()
             else:
                 for n in missing:
                     if self.params[n].grad is None:
                         self.grad_views[n].zero_()
         for n in missing:
             self.params[n].grad = self.grad_views[n]
+
+    def _attach_some(self, zero, frozen):
+        fresh = []
+        for n, v in self.grad_views.items():
+            p = self.params[n]
+            if n in frozen:
+                if p.grad is v:
+                    p.grad = None
+            elif p.grad is not v:
+                if zero and p.grad is None:
+                    fresh.append(n)
+                p.grad = v
+        if fresh:       # their gradients restart from zero (and drop what a frozen step left there)
+            for s, e in self.name_ranges(frozenset(fresh)):
+                self.grad[s:e].zero_()
+            self._dirty.difference_update(fresh)
 
     def wait_update(self, stream=None):
         """make `stream` (default: the current stream) wait for an overlapped optimizer update
@@ -235,7 +374,7 @@ class Arena:
         self.wait_update()
         self.grad.zero_()
         self.attach_grads(zero=False)
-        self.ld_touched.clear()
+        self.cleared()
 
     def ranges_of(self, prefix):
         """merged [start, end) arena ranges of the parameters whose names start with prefix"""

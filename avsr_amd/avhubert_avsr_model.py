@@ -32,8 +32,8 @@ class _E2EStep(torch.autograd.Function):
     Engine.backward (weight gradients land in the arena; no graph inside the model)."""
 
     @staticmethod
-    def forward(fctx, anchor, engine, videos, audios, video_lengths, labels, train):
-        out4, ectx = engine.forward(videos, audios, video_lengths, labels, train=train, need_grad=True)
+    def forward(fctx, anchor, engine, videos, audios, video_lengths, labels, train, snap):
+        out4, ectx = engine.forward(videos, audios, video_lengths, labels, train=train, need_grad=True, snap=snap)
         fctx.engine, fctx.ectx = engine, ectx
         fctx.mtl = engine.cfg.mtlalpha
         return out4[0].clone(), out4[1].clone(), out4[2].clone(), out4[3].clone()
@@ -44,11 +44,12 @@ class _E2EStep(torch.autograd.Function):
         dloss = z if dloss is None else dloss
         d_ctc = dloss * fctx.mtl + (z if dctc is None else dctc)
         d_att = dloss * (1.0 - fctx.mtl) + (z if datt is None else datt)
-        # a per-parameter optimizer may have reset .grad to None since the last step
-        fctx.engine.arena.attach_grads()
+        # a per-parameter optimizer may have reset .grad to None since the last step; a parameter
+        # frozen when the forward ran (requires_grad=False) gets no gradient: its .grad stays None
+        fctx.engine.arena.attach_grads(snap=fctx.ectx["snap"])
         fctx.engine.backward(fctx.ectx, d_ctc, d_att)
         fctx.ectx = None
-        return (None,) * 7
+        return (None,) * 8
 
 
 class E2E(E2EShell):
@@ -81,8 +82,11 @@ class E2E(E2EShell):
 
     def forward(self, video, audio, video_lengths, audio_lengths, label):
         eng = self.engine()
-        if torch.is_grad_enabled():
-            return _E2EStep.apply(self._anchor, eng, video, audio, video_lengths, label, self.training)
+        # which parameters train (requires_grad; feature_grad_mult = 0 freezes both frontends): the
+        # step's backward follows this snapshot. With none there is no graph, as in torch
+        snap = eng.trainable() if torch.is_grad_enabled() else None
+        if snap is not None and snap.any:
+            return _E2EStep.apply(self._anchor, eng, video, audio, video_lengths, label, self.training, snap)
         out4, _ = eng.forward(video, audio, video_lengths, label, train=self.training, need_grad=False)
         return out4[0].clone(), out4[1].clone(), out4[2].clone(), out4[3].clone()
 

@@ -122,6 +122,17 @@ def _pad8(n):
     return (n + 7) // 8 * 8
 
 
+class _Plan:
+    """What a step does under a Trainable with frozen parameters (requires_grad=False; Engine._plan).
+    fz: the frozen names; cut: the first encoder unit (in forward order: 0 the two frontends,
+    1 fusion LayerNorm + post_extract_proj, 2 pos-conv, 3 + i encoder layer i, 3 + nl the final
+    LayerNorm) with a trainable parameter — the units below it are neither saved for nor reached by
+    the backward (cut = 4 + nl: the whole encoder is frozen); resnet / dec / ctc: some parameter of
+    the ResNet / the decoder / the CTC head trains; dirty: frozen names above the cut, whose ranges
+    the fused epilogues of the unchanged data-gradient chain may still write."""
+    __slots__ = ("fz", "cut", "enc", "resnet", "dec", "ctc", "dirty")
+
+
 class _Seeds:
     """deterministic per-site dropout stream ids for one step"""
 
@@ -258,6 +269,12 @@ class Engine:
             self._layer_decay_off.append(min(offs) if offs else d1)
         if self.layerdrop > 0:      # the optimizer skips the layers no backward touched (grad None)
             self.arena.ld_ranges = [self.arena.ranges_of(f"encoder.encoder.layers.{i}.") for i in range(self.nl)]
+        # requires_grad=False: the frozen names of the backward in progress (None: nothing frozen)
+        self._fz = None
+        EN = "encoder."
+        self._units = ([(EN + "feature_extractor_audio.", EN + "feature_extractor_video."),
+                        (EN + "layer_norm.", EN + "post_extract_proj."), (self.pc,)]
+                       + [(f"{E}.{i}.",) for i in range(self.nl)] + [(EN + "encoder.layer_norm.",)])
         self.shell = shell
         self.step_count = 0
         self._pe = positional_encoding(max(512, 64), self.dD, self.device)
@@ -308,6 +325,44 @@ class Engine:
 
     def g(self, n):
         return self.arena.g(n)
+
+    # ------------------------------------------------------------- requires_grad=False
+    FRONT = ("encoder.feature_extractor_audio.", "encoder.feature_extractor_video.")
+
+    def trainable(self):
+        """arena.snapshot() with cfg.feature_grad_mult == 0 read as "both frontends frozen" (the
+        reference runs them under torch.no_grad() then, avhubert.py:395-404)"""
+        self.arena.also_frozen = self.FRONT if self.cfg.feature_grad_mult == 0 else ()
+        return self.arena.snapshot()
+
+    def _plan(self, snap):
+        """the _Plan of a Trainable (None: nothing frozen, every path as without the feature);
+        computed once per distinct frozen set and kept on the snapshot"""
+        if snap is None or snap.all:
+            return None
+        if snap.plan is None:
+            fz = snap.frozen
+            names = self.arena.grad_views
+            live = [[n for n in names if n.startswith(pre) and n not in fz] for pre in self._units]
+            p = _Plan()
+            p.fz = fz
+            p.cut = next((u for u, l in enumerate(live) if l), len(live))
+            p.enc = p.cut < len(live)
+            p.resnet = any(n.startswith("encoder.feature_extractor_video.resnet.") for n in live[0])
+            p.dec = any(n.startswith("decoder.") and n not in fz for n in names)
+            p.ctc = any(n.startswith("ctc.") and n not in fz for n in names)
+            below = tuple(pre for u in self._units[:p.cut] for pre in u)
+            if not p.resnet:
+                below += ("encoder.feature_extractor_video.resnet.",)
+            p.dirty = frozenset(n for n in fz if not n.startswith(below))
+            snap.plan = p
+        return snap.plan
+
+    def _live(self, *names):
+        """some of these (adjacent, jointly computed) parameters gets a gradient in this backward:
+        the stand-alone gradient launches of frozen parameters are not issued"""
+        fz = self._fz
+        return fz is None or any(n not in fz for n in names)
 
     def _bn(self, prefix):
         """(module, gamma, beta master fp32 views) of a BatchNorm with the given key prefix."""
@@ -386,7 +441,8 @@ class Engine:
                 g.zero_()
         self._on_side(clear, g)
         self.arena.attach_grads(zero=False)
-        self.arena.ld_touched.clear()
+        # done: the update zeroed what it read, and what fused epilogues left in frozen ranges
+        self.arena.cleared(everything=not done)
 
     def join_side(self):
         """make the current stream wait for every weight gradient issued so far"""
@@ -670,7 +726,8 @@ class Engine:
             dhd = self._e(M2, cout) if down else None
             ops.bn_bwd_apply(dz2, blk["h2"], blk["st2"], sums2, dh2, res=res, st2=rst, dh2=dhd)
             # conv2 (its data-grad carries bn1 + prelu1's reduction when fused)
-            self._conv_wgrad(blk["g2"], blk["a1"], dh2, self.g(p + "conv2.weight"))
+            if self._live(p + "conv2.weight"):
+                self._conv_wgrad(blk["g2"], blk["a1"], dh2, self.g(p + "conv2.weight"))
             da1 = self._e(M2, cout)
             g1 = dict(dprelu=self.g(p + "relu1.weight"), dgamma=self.g(p + "bn1.weight"), dbeta=self.g(p + "bn1.bias"))
             prelu1 = self.arena.master(p + "relu1.weight")
@@ -683,7 +740,8 @@ class Engine:
                 dz1, sums1 = ops.bn_act_bwd_reduce(da1, blk["h1"], blk["st1"], prelu1, **g1)
             dh1 = self._e(M2, cout)
             ops.bn_bwd_apply(dz1, blk["h1"], blk["st1"], sums1, dh1)
-            self._conv_wgrad(blk["g1"], blk["x"], dh1, self.g(p + "conv1.weight"))
+            if self._live(p + "conv1.weight"):
+                self._conv_wgrad(blk["g1"], blk["x"], dh1, self.g(p + "conv1.weight"))
             # block input gradient: conv1 (+ downsample) data-grads (+ dz2 through an identity
             # shortcut); the last one carries the reduction of the layer that produced the input
             if fuse:
@@ -704,7 +762,8 @@ class Engine:
             else:
                 dx = self._e(blk["x"].shape[0], cin)
                 ops.conv_bwd_data(blk["g1"], dh1, self.w(p + "conv1.weight"), dx)
-                self._conv_wgrad(blk["gd"], blk["x"], dhd, self.g(p + "downsample.0.weight"))
+                if self._live(p + "downsample.0.weight"):
+                    self._conv_wgrad(blk["gd"], blk["x"], dhd, self.g(p + "downsample.0.weight"))
                 if fuse:
                     red = ops.conv_bwd_data_bnr(blk["gd"], dhd, self.w(p + "downsample.0.weight"), dx, beta=1.0, **tgt)
                 else:
@@ -720,9 +779,10 @@ class Engine:
                                              dgamma=self.g(R + "frontend3D.1.weight"),
                                              dbeta=self.g(R + "frontend3D.1.bias"), reduced=red)
         ops.stem_pool_bwd_apply(dzp, ctx["am"], ctx["h0"], N, 44, 44, ctx["st0"], sums, dh0)
-        gp = self._z(64, 7, 7, 8, dtype=torch.float32)
-        ops.conv_bwd_weight(ctx["gs"], ctx["xp"], dh0, gp)
-        ops.stem_wgrad_unpack(gp, self.g(R + "frontend3D.0.weight"))
+        if self._live(R + "frontend3D.0.weight"):
+            gp = self._z(64, 7, 7, 8, dtype=torch.float32)
+            ops.conv_bwd_weight(ctx["gs"], ctx["xp"], dh0, gp)
+            ops.stem_wgrad_unpack(gp, self.g(R + "frontend3D.0.weight"))
 
     # ============================================================================ encoder
     def _ln(self, x, name, eps, save=None):
@@ -745,13 +805,15 @@ class Engine:
             ops.ew_bwd(out, out=g, drop_p=p, seed=seed, db=self.g(dbn))
         return out
 
-    def encoder_fwd(self, audios, videos, bt, train, save, seeds, modality=None):
-        """AVHubertModel.forward_gen(features_only=True) — returns (x (M, D), ctx)."""
+    def encoder_fwd(self, audios, videos, bt, train, save, seeds, modality=None, plan=None):
+        """AVHubertModel.forward_gen(features_only=True) — returns (x (M, D), ctx). plan: the
+        _Plan of a step with frozen parameters; nothing is saved for the units below its cut."""
         cfg = self.cfg
         B, T = bt["B"], bt["T"]
         M, D = B * T, self.D
         EN = "encoder."
-        ctx = {"B": B, "T": T, "modality": modality}
+        cut = 0 if plan is None else plan.cut
+        ctx = {"B": B, "T": T, "modality": modality, "plan": plan}
         # LayerDrop: one torch.rand([]) (CPU generator) per layer on every call, train or eval, as
         # the reference draws them (avhubert.py:709-712; no other torch CPU draw happens between
         # the reference's frontends and its layer loop); training skips a layer whose draw is below
@@ -778,7 +840,8 @@ class Engine:
         # video_off: the ResNet gradient is exactly zero (avhubert.py:480), so nothing of its
         # forward is kept for a backward (no packed stem input, no pooled-grid argmax values);
         # the forward itself still runs for the BatchNorm running statistics, as in the reference
-        feat, vctx = self.video_fwd(videos, train, save and modality != "video_off")
+        # (a frozen ResNet likewise: requires_grad=False on all of it, or feature_grad_mult = 0)
+        feat, vctx = self.video_fwd(videos, train, save and modality != "video_off" and (plan is None or plan.resnet))
         if modality == "video_off":
             if add:
                 fcat.copy_(fa)
@@ -819,8 +882,13 @@ class Engine:
         if p_h > 0:
             ops.dropout_fwd(y, y, p_h, sd_pc)
         if save:
-            ctx.update(ain=ain, fcat=fcat, ln0=ln0, m0=m0, r0=r0, sd_in=sd_in, p_in=p_in, x_pre=x, geo=geo, wpc=wpc,
-                       norm=norm, pre=pre, sd_pc=sd_pc, p_h=p_h, vctx=vctx, feat=feat, klen=klen)
+            ctx.update(klen=klen)
+            if cut <= 0:
+                ctx.update(ain=ain, vctx=vctx, feat=feat)
+            if cut <= 1:
+                ctx.update(fcat=fcat, ln0=ln0, m0=m0, r0=r0, sd_in=sd_in, p_in=p_in)
+            if cut <= 2:
+                ctx.update(x_pre=x, geo=geo, wpc=wpc, norm=norm, pre=pre, sd_pc=sd_pc, p_h=p_h)
         x = y
         layers = []
         for i in range(self.nl):
@@ -828,7 +896,8 @@ class Engine:
                 if save:
                     layers.append(None)
                 continue
-            x, lc = self._enc_layer_fwd(i, x, B, T, klen, train, save, seeds, amask.get(i))
+            # a layer below the cut keeps nothing (lc None, like a layer LayerDrop skipped)
+            x, lc = self._enc_layer_fwd(i, x, B, T, klen, train, save and 3 + i >= cut, seeds, amask.get(i))
             if save:
                 layers.append(lc)
         E = "encoder.encoder."
@@ -930,19 +999,25 @@ class Engine:
         def tag(t):
             if tags is not None and len(self._side_defer) == base + len(tags) + 1:
                 tags.append(t)
-        self._wgrad(g2, lc["act"], self.g(ff + "output_dense.weight"))
+        if self._live(ff + "output_dense.weight"):
+            self._wgrad(g2, lc["act"], self.g(ff + "output_dense.weight"))
         tag("f2")
         dh = ops.linear_dgrad(g2, self.w(ff + "output_dense.weight"), gate=lc["h"], act=GELU, drop_p=lc["p_a"],
                               seed=lc["sd_a"], db=self._fused_db(ff + "intermediate_dense.bias"))
         self._bias_grad(dh, self.g(ff + "intermediate_dense.bias"), fused=True)
-        self._wgrad(dh, lc["ln2"], self.g(ff + "intermediate_dense.weight"))
+        if self._live(ff + "intermediate_dense.weight"):
+            self._wgrad(dh, lc["ln2"], self.g(ff + "intermediate_dense.weight"))
         tag("f1")
         dln2 = ops.linear_dgrad(dh, self.w(ff + "intermediate_dense.weight"))
         # x1 = x + drop(o Wo^T + bo): the out-proj dropout backward rides on this LN backward
         go = self._e(M, D)              # fresh: g2 may still be read by the side stream
         dx1 = self._ln_bwd(dln2, lc["x1"], p + "final_layer_norm", lc["m2"], lc["r2"], dres=dx2, dx=dx2,
                            ew=(go, lc["p_h"], lc["sd_o"], a + "out_proj.bias"))
-        if not WGRAD_GROUP:
+        names_b = [a + "q_proj.bias", a + "k_proj.bias", a + "v_proj.bias"]
+        names_w = [a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"]
+        # (the grouped launch only when both of its members get a gradient)
+        grouped = WGRAD_GROUP and self._live(*names_w) and self._live(a + "out_proj.weight")
+        if not grouped and self._live(a + "out_proj.weight"):
             self._wgrad(go, lc["o"], self.g(a + "out_proj.weight"))
             tag("o")
         do = ops.linear_dgrad(go, self.w(a + "out_proj.weight"))
@@ -951,8 +1026,6 @@ class Engine:
         dqkv = self._e(M, 3 * D)
         dq32 = self._dq32(M, D)
         delta = self._e(B, H, T, dtype=torch.float32)
-        names_b = [a + "q_proj.bias", a + "k_proj.bias", a + "v_proj.bias"]
-        names_w = [a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"]
         db_qkv = self.arena.span(names_b, buf="g")
         ops.attn_bwd(do, qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], lc["o"], lc["lse"], dq32, dqkv[:, D:2 * D],
                      dqkv[:, 2 * D:], delta, B=B, H=H, Lq=T, Lk=T, klen=klen, scale=0.125, drop_p=lc["p_att"],
@@ -960,14 +1033,15 @@ class Engine:
         if dq32 is not None:
             ops.cast(dq32, dqkv[:, :D])
         # the q/k/v bias gradients (column sums of dqkv) on the side stream
-        self._bias_grad_side(dqkv, db_qkv)
+        if self._live(*names_b):
+            self._bias_grad_side(dqkv, db_qkv)
         tag("c")
-        if WGRAD_GROUP:     # QKV (192 tiles) and out-proj (64 tiles) weight-gradients in one launch
+        if grouped:         # QKV (192 tiles) and out-proj (64 tiles) weight-gradients in one launch
             dwq, dwo = self.arena.span(names_w, buf="g"), self.g(a + "out_proj.weight")
             o = lc["o"]
             ln1 = lc["ln1"]
             self._on_side(lambda: ops.wgrad_group([(dqkv, ln1, dwq, 1.0), (go, o, dwo, 1.0)]), dqkv, ln1, go, o)
-        else:
+        elif self._live(*names_w):
             self._wgrad(dqkv, lc["ln1"], self.arena.span(names_w, buf="g"))
         tag("q")
         if tags is not None and SIDE_ORDER:
@@ -988,8 +1062,11 @@ class Engine:
         M, D = B * T, self.D
         EN = "encoder."
         E = "encoder.encoder."
+        # frozen parameters (requires_grad=False): nothing below the plan's cut is reached
+        plan = ctx.get("plan")
+        cut = 0 if plan is None else plan.cut
         layers = ctx["layers"]
-        ex = [i for i in range(self.nl) if layers[i] is not None]       # layers LayerDrop kept
+        ex = [i for i in range(self.nl) if layers[i] is not None]       # layers LayerDrop kept (above the cut)
         self.arena.ld_touched.update(ex)
         ew = self._ew_next(ex[-1], layers[ex[-1]], M) if ex else None
         dx = self._ln_bwd(dout, ctx["x_last"], E + "layer_norm", ctx["mf"], ctx["rf"], ew=ew)
@@ -1004,19 +1081,24 @@ class Engine:
                 ops.colsum_flush()                  # this layer's bias / LayerNorm gradients
             if self.on_grad_ready is not None:      # layers >= i (and everything after them) final
                 self.on_grad_ready(self._layer_decay_off[i])   # (the reducer also waits for the side stream)
+        if cut > 2:                 # the first trainable unit is an encoder layer or the final LayerNorm
+            return self._encoder_bwd_end()
         # pos-conv block: x0 = drop(x + gelu(conv(x) + b))
         pc = self.pc
         if ctx["p_h"] > 0:
             ops.ew_bwd(dx, out=dx, drop_p=ctx["p_h"], seed=ctx["sd_pc"])
         gp = self._e(M, D)
         ops.ew_bwd(dx, out=gp, gate=ctx["pre"], act=GELU, db=self.g(pc + "bias"))
-        dwpc = self._z(D, self.PK, D // self.G, dtype=torch.float32)
-        ops.conv_bwd_weight(ctx["geo"], ctx["x_pre"], gp, dwpc)
-        ops.weightnorm_bwd(self.arena.master(pc + "parametrizations.weight.original1"),
-                           self.arena.master(pc + "parametrizations.weight.original0").reshape(-1), ctx["norm"], dwpc,
-                           self.g(pc + "parametrizations.weight.original1"),
-                           self.g(pc + "parametrizations.weight.original0").reshape(-1),
-                           self._e(self.PK, dtype=torch.float32))
+        if self._live(pc + "parametrizations.weight.original1", pc + "parametrizations.weight.original0"):
+            dwpc = self._z(D, self.PK, D // self.G, dtype=torch.float32)
+            ops.conv_bwd_weight(ctx["geo"], ctx["x_pre"], gp, dwpc)
+            ops.weightnorm_bwd(self.arena.master(pc + "parametrizations.weight.original1"),
+                               self.arena.master(pc + "parametrizations.weight.original0").reshape(-1), ctx["norm"], dwpc,
+                               self.g(pc + "parametrizations.weight.original1"),
+                               self.g(pc + "parametrizations.weight.original0").reshape(-1),
+                               self._e(self.PK, dtype=torch.float32))
+        if cut == 2:
+            return self._encoder_bwd_end()
         ops.conv_bwd_data(ctx["geo"], gp, ctx["wpc"], dx, beta=1.0)
         if ctx["klen"] is not None:
             ops.mask_rows(dx, B, T, ctx["klen"])
@@ -1027,20 +1109,31 @@ class Engine:
             dln0 = gi
         else:
             ops.ew_bwd(dx, out=gi, drop_p=ctx["p_in"], seed=ctx["sd_in"], db=self.g(EN + "post_extract_proj.bias"))
-            self._wgrad(gi, ctx["ln0"], self.g(EN + "post_extract_proj.weight"))
+            if self._live(EN + "post_extract_proj.weight"):
+                self._wgrad(gi, ctx["ln0"], self.g(EN + "post_extract_proj.weight"))
+            if cut == 1 and not self._live(EN + "layer_norm.weight", EN + "layer_norm.bias"):
+                return self._encoder_bwd_end()
             dln0 = ops.linear_dgrad(gi, self.w(EN + "post_extract_proj.weight"))
         dfcat = self._ln_bwd(dln0, ctx["fcat"], EN + "layer_norm", ctx["m0"], ctx["r0"])
+        if cut == 1:                # both frontends frozen (requires_grad=False or feature_grad_mult = 0)
+            return self._encoder_bwd_end()
         fgm = cfg.feature_grad_mult            # GradMultiply (avhubert.py:173-182) on both frontends
         # 'add': both streams receive the sum's gradient; 'concat': each its half
         da_all, dv_all = (dfcat, dfcat) if self.fuse_add else (dfcat[:, :D], dfcat[:, D:])
         if ctx["modality"] != "audio_off":
             da = da_all
-            self._bias_grad(da, self.g(EN + "feature_extractor_audio.proj.bias"), alpha=fgm)
-            self._wgrad(da, ctx["ain"], self.g(EN + "feature_extractor_audio.proj.weight"), alpha=fgm)
+            if self._live(EN + "feature_extractor_audio.proj.bias"):
+                self._bias_grad(da, self.g(EN + "feature_extractor_audio.proj.bias"), alpha=fgm)
+            if self._live(EN + "feature_extractor_audio.proj.weight"):
+                self._wgrad(da, ctx["ain"], self.g(EN + "feature_extractor_audio.proj.weight"), alpha=fgm)
         if ctx["modality"] != "video_off":
             dv = dv_all
-            self._bias_grad(dv, self.g(EN + "feature_extractor_video.proj.bias"), alpha=fgm)
-            self._wgrad(dv, ctx["feat"], self.g(EN + "feature_extractor_video.proj.weight"), alpha=fgm)
+            if self._live(EN + "feature_extractor_video.proj.bias"):
+                self._bias_grad(dv, self.g(EN + "feature_extractor_video.proj.bias"), alpha=fgm)
+            if self._live(EN + "feature_extractor_video.proj.weight"):
+                self._wgrad(dv, ctx["feat"], self.g(EN + "feature_extractor_video.proj.weight"), alpha=fgm)
+        # the ResNet branch on its own: frozen as a whole, there is no data gradient into it
+        if ctx["modality"] != "video_off" and (plan is None or plan.resnet):
             dfeat = self._e(M, 512)
             ops.gemm(dv, self.w(EN + "feature_extractor_video.proj.weight"), dfeat, M=M, N=512, K=D, a_kmajor=True,
                      b_kmajor=False, lda=dv.stride(0), ldb=512, ldc=512, alpha=fgm)
@@ -1048,6 +1141,11 @@ class Engine:
             self.video_bwd(ctx["vctx"], dfeat)
         else:
             self._grads_before_video()
+        self.join_side()
+
+    def _encoder_bwd_end(self):
+        """the encoder backward stops here (everything further down is frozen)"""
+        self._grads_before_video()
         self.join_side()
 
     def _grads_before_video(self):
@@ -1124,8 +1222,11 @@ class Engine:
         R, D, H = B * L1, self.dD, self.dH
         klen = ctx["klen"]
         p_d, p_att = ctx["p_d"], ctx["p_att"]
-        self._bias_grad(dlogits, self.arena.g_padded("decoder.output_layer.bias"))
-        self._wgrad(dlogits, ctx["yn"], self.arena.g_padded("decoder.output_layer.weight"))   # padded vocab
+        live = self._live
+        if live("decoder.output_layer.bias"):
+            self._bias_grad(dlogits, self.arena.g_padded("decoder.output_layer.bias"))
+        if live("decoder.output_layer.weight"):
+            self._wgrad(dlogits, ctx["yn"], self.arena.g_padded("decoder.output_layer.weight"))   # padded vocab
         dyn = self._e(R, D)
         ops.gemm(dlogits, self.arena.w_padded("decoder.output_layer.weight"), dyn, M=R, N=D, K=self.Vp, a_kmajor=True,
                  b_kmajor=False, lda=dlogits.stride(0), ldb=D, ldc=D)
@@ -1158,15 +1259,18 @@ class Engine:
             sa, ca, ff = p + "self_attn.", p + "src_attn.", p + "feed_forward."
             # FFN: g = the output dropout backward of dy (with w_2's bias gradient), fused into the
             # LayerNorm backward that produced dy
-            self._wgrad(g, lc["a"], self.g(ff + "w_2.weight"))
+            if live(ff + "w_2.weight"):
+                self._wgrad(g, lc["a"], self.g(ff + "w_2.weight"))
             dh = ops.linear_dgrad(g, self.w(ff + "w_2.weight"), gate=lc["h"], act=RELU, drop_p=p_d, seed=lc["s5"],
                                   db=self._fused_db(ff + "w_1.bias"))
             self._bias_grad(dh, self.g(ff + "w_1.bias"), fused=True)
-            self._wgrad(dh, lc["n3"], self.g(ff + "w_1.weight"))
+            if live(ff + "w_1.weight"):
+                self._wgrad(dh, lc["n3"], self.g(ff + "w_1.weight"))
             dn3 = ops.linear_dgrad(dh, self.w(ff + "w_1.weight"))
             dy, g = ln_bwd(dn3, lc["y2"], p + "norm3", lc["m3"], lc["r3"], dy, ew_of(i, "s4", "src_attn.linear_out.bias"))
             # source attention
-            self._wgrad(g, lc["o2"], self.g(ca + "linear_out.weight"))
+            if live(ca + "linear_out.weight"):
+                self._wgrad(g, lc["o2"], self.g(ca + "linear_out.weight"))
             do2 = ops.linear_dgrad(g, self.w(ca + "linear_out.weight"))
             dkv = self._e(B * T, 2 * D)
             dq32 = self._dq32(R, D)
@@ -1177,16 +1281,22 @@ class Engine:
                          dq=None if dq32 is not None else dq2)
             if dq32 is not None:
                 ops.cast(dq32, dq2)
-            self._bias_grad(dq2, self.g(ca + "linear_q.bias"))
-            self._wgrad(dq2, lc["n2"], self.g(ca + "linear_q.weight"))
+            if live(ca + "linear_q.bias"):
+                self._bias_grad(dq2, self.g(ca + "linear_q.bias"))
+            if live(ca + "linear_q.weight"):
+                self._wgrad(dq2, lc["n2"], self.g(ca + "linear_q.weight"))
             dn2 = ops.linear_dgrad(dq2, self.w(ca + "linear_q.weight"))
             kvw = [ca + "linear_k.weight", ca + "linear_v.weight"]
-            self._bias_grad(dkv, self.arena.span([ca + "linear_k.bias", ca + "linear_v.bias"], buf="g"))
-            self._wgrad(dkv, enc, self.arena.span(kvw, buf="g"))
-            ops.linear_dgrad(dkv, self.arena.span(kvw), out=denc, beta=1.0)
+            if live(ca + "linear_k.bias", ca + "linear_v.bias"):
+                self._bias_grad(dkv, self.arena.span([ca + "linear_k.bias", ca + "linear_v.bias"], buf="g"))
+            if live(*kvw):
+                self._wgrad(dkv, enc, self.arena.span(kvw, buf="g"))
+            if denc is not None:        # None: the whole encoder is frozen, nobody reads d(memory)
+                ops.linear_dgrad(dkv, self.arena.span(kvw), out=denc, beta=1.0)
             dy, g = ln_bwd(dn2, lc["y1"], p + "norm2", lc["m2"], lc["r2"], dy, ew_of(i, "s2", "self_attn.linear_out.bias"))
             # causal self attention
-            self._wgrad(g, lc["o1"], self.g(sa + "linear_out.weight"))
+            if live(sa + "linear_out.weight"):
+                self._wgrad(g, lc["o1"], self.g(sa + "linear_out.weight"))
             do1 = ops.linear_dgrad(g, self.w(sa + "linear_out.weight"))
             dqkv = self._e(R, 3 * D)
             dq32 = self._dq32(R, D)
@@ -1199,18 +1309,28 @@ class Engine:
                 ops.cast(dq32, dqkv[:, :D])
             nb = [sa + "linear_q.bias", sa + "linear_k.bias", sa + "linear_v.bias"]
             nw = [sa + "linear_q.weight", sa + "linear_k.weight", sa + "linear_v.weight"]
-            self._bias_grad(dqkv, self.arena.span(nb, buf="g"))
-            self._wgrad(dqkv, lc["n1"], self.arena.span(nw, buf="g"))
+            if live(*nb):
+                self._bias_grad(dqkv, self.arena.span(nb, buf="g"))
+            if live(*nw):
+                self._wgrad(dqkv, lc["n1"], self.arena.span(nw, buf="g"))
             dn1 = ops.linear_dgrad(dqkv, self.arena.span(nw))
             dy, g = ln_bwd(dn1, lc["y"], p + "norm1", lc["m1"], lc["r1"], dy,
                            ew_of(i - 1, "s6", "feed_forward.w_2.bias") if i > 0 else None)
         self._side_layer(False)
-        ops.embed_bwd(bt["ys_in"], dy, math.sqrt(D), self.g("decoder.embed.0.weight"), L1, drop_p=p_d, seed=ctx["sd_e"])
+        if live("decoder.embed.0.weight"):
+            ops.embed_bwd(bt["ys_in"], dy, math.sqrt(D), self.g("decoder.embed.0.weight"), L1, drop_p=p_d, seed=ctx["sd_e"])
 
     # ======================================================================== full model
-    def forward(self, videos, audios, video_lengths, labels, train=True, need_grad=True, seed=None):
-        """E2E.forward: returns (out4 = [loss, loss_ctc, loss_att, acc] on device, ctx)."""
+    def forward(self, videos, audios, video_lengths, labels, train=True, need_grad=True, seed=None, snap=None):
+        """E2E.forward: returns (out4 = [loss, loss_ctc, loss_att, acc] on device, ctx). The
+        context carries the snapshot of which parameters train (snap; default: taken here): the
+        backward follows it. With nothing trainable there is no context (need_grad=False)."""
         cfg = self.cfg
+        plan = None
+        if need_grad:
+            snap = snap or self.trainable()
+            plan = self._plan(snap)
+            need_grad = snap.any
         if train and need_grad and self.before_forward is not None:
             self.before_forward()
         seeds = self.new_seeds(seed)
@@ -1219,7 +1339,8 @@ class Engine:
         M = B * T
         modality = self.draw_modality(train) if self.force_modality is None else self.force_modality[0]
         self.last_modality = modality
-        enc, ectx = self.encoder_fwd(audios.to(self.device), videos.to(self.device), bt, train, need_grad, seeds, modality)
+        enc, ectx = self.encoder_fwd(audios.to(self.device), videos.to(self.device), bt, train,
+                                     need_grad and (plan is None or plan.enc), seeds, modality, plan=plan)
         # CTC branch: ctc_lo(dropout(enc)). It runs on the side stream (idle during the forward),
         # beside the decoder forward, whose small launches leave most CUs free; buffers are
         # allocated on the step stream, which waits for the branch before the loss combine
@@ -1247,7 +1368,7 @@ class Engine:
         else:
             ctc_branch()
         # attention branch
-        dlog, dctx = self.decoder_fwd(enc, bt, train, need_grad, seeds)
+        dlog, dctx = self.decoder_fwd(enc, bt, train, need_grad and (plan is None or plan.enc or plan.dec), seeds)
         self.join_side()
         R = dlog.shape[0]
         dlse = self._e(R, dtype=torch.float32)
@@ -1261,7 +1382,7 @@ class Engine:
         ctx = None
         if need_grad:
             ctx = dict(bt=bt, enc=enc, ectx=ectx, xin=xin, p_c=p_c, sd_c=sd_c, clog=clog, cp=cp, dlog=dlog, dctx=dctx,
-                       dlse=dlse)
+                       dlse=dlse, snap=snap, plan=plan)
         return out4, ctx
 
     def backward(self, ctx, d_ctc, d_att):
@@ -1275,6 +1396,7 @@ class Engine:
         d_ctc = d_ctc.reshape(1).to(torch.float32)
         d_att = d_att.reshape(1).to(torch.float32)
         self.join_side()            # a gradient clear queued on the side stream (zero_grad_async)
+        self._begin_backward(ctx.get("snap"))
         if self.before_backward is not None:
             self.before_backward()
         # bias / LayerNorm parameter-gradient finalise passes are batched: one launch per
@@ -1285,6 +1407,7 @@ class Engine:
             ops.colsum_flush()
         finally:
             ops.colsum_defer(prev)
+            self._fz = None
         if self.after_backward is not None:
             self.after_backward()
         self.join_side()
@@ -1295,6 +1418,7 @@ class Engine:
         # as in backward(): the side stream's work from the forward (the bf16 stem's packed
         # input for its weight-grad, a zero_grad_async clear) must land before the first write
         self.join_side()
+        self._begin_backward(ectx.get("snap"))
         if self.before_backward is not None:
             self.before_backward()
         prev = ops.colsum_defer(_COLSUM_DEFER)
@@ -1303,36 +1427,59 @@ class Engine:
             ops.colsum_flush()
         finally:
             ops.colsum_defer(prev)
+            self._fz = None
         if self.after_backward is not None:
             self.after_backward()
         self.join_side()
+
+    def _begin_backward(self, snap):
+        """this backward follows the forward's snapshot of what trains: the arena records the
+        ranges it leaves without a gradient (and that arena.grads_cleared no longer holds)"""
+        plan = self._plan(snap)
+        self._fz = None if plan is None else plan.fz
+        self.arena.begin_backward(snap, plan.dirty if plan is not None else ())
 
     def _backward(self, ctx, d_ctc, d_att):
         cfg = self.cfg
         bt = ctx["bt"]
         B, T = bt["B"], bt["T"]
         M = B * T
+        # frozen parameters (requires_grad=False): a branch runs when one of its own parameters
+        # trains or the (partly) trainable encoder below needs its data gradient
+        plan = ctx.get("plan")
+        enc_on = plan is None or plan.enc
+        dec_on = enc_on or plan.dec
+        ctc_on = enc_on or plan.ctc
         # attention loss -> decoder
-        dl = ctx["dlog"]
-        ddl = self._e(dl.shape[0], self.Vp)
-        if self.len_norm:      # / the number of target tokens (device count, no host sync)
-            d_att = d_att / (bt["ys_out"] != -1).sum().clamp_min(1).to(torch.float32)
-            ops.lsm_bwd(dl, self.V, bt["ys_out"], cfg.lsm_weight, ctx["dlse"], d_att, 1.0, ddl)
-        else:
-            ops.lsm_bwd(dl, self.V, bt["ys_out"], cfg.lsm_weight, ctx["dlse"], d_att, 1.0 / B, ddl)
-        denc = self._e(M, self.D)
+        if dec_on:
+            dl = ctx["dlog"]
+            ddl = self._e(dl.shape[0], self.Vp)
+            if self.len_norm:      # / the number of target tokens (device count, no host sync)
+                d_att = d_att / (bt["ys_out"] != -1).sum().clamp_min(1).to(torch.float32)
+                ops.lsm_bwd(dl, self.V, bt["ys_out"], cfg.lsm_weight, ctx["dlse"], d_att, 1.0, ddl)
+            else:
+                ops.lsm_bwd(dl, self.V, bt["ys_out"], cfg.lsm_weight, ctx["dlse"], d_att, 1.0 / B, ddl)
+        denc = self._e(M, self.D) if enc_on else None
         # CTC -> denc (first write), then decoder adds
-        dcl = self._e(M, self.Vp)
-        ops.ctc_bwd(ctx["cp"], d_ctc, 1.0 / B, dcl)
-        self._bias_grad(dcl, self.arena.g_padded("ctc.ctc_lo.bias"))
-        # padded vocab (the backward writes zeros to columns V..Vp): Vp rows keep the weight-grad on
-        # the LDS-DMA core (r-contiguous operands need a multiple of 8); the pad rows get exact zeros
-        self._wgrad(dcl, ctx["xin"], self.arena.g_padded("ctc.ctc_lo.weight"))
-        ops.gemm(dcl, self.arena.w_padded("ctc.ctc_lo.weight"), denc, M=M, N=self.D, K=self.Vp, a_kmajor=True,
-                 b_kmajor=False, lda=dcl.stride(0), ldb=self.D, ldc=self.D, epi_bwd=True, drop_p=ctx["p_c"],
-                 seed=ctx["sd_c"])
-        self.decoder_bwd(ctx["dctx"], ddl, ctx["enc"], denc, bt)
-        self.encoder_bwd(ctx["ectx"], denc)
+        if ctc_on:
+            dcl = self._e(M, self.Vp)
+            ops.ctc_bwd(ctx["cp"], d_ctc, 1.0 / B, dcl)
+            if self._live("ctc.ctc_lo.bias"):
+                self._bias_grad(dcl, self.arena.g_padded("ctc.ctc_lo.bias"))
+            # padded vocab (the backward writes zeros to columns V..Vp): Vp rows keep the weight-grad on
+            # the LDS-DMA core (r-contiguous operands need a multiple of 8); the pad rows get exact zeros
+            if self._live("ctc.ctc_lo.weight"):
+                self._wgrad(dcl, ctx["xin"], self.arena.g_padded("ctc.ctc_lo.weight"))
+        if enc_on:
+            ops.gemm(dcl, self.arena.w_padded("ctc.ctc_lo.weight"), denc, M=M, N=self.D, K=self.Vp, a_kmajor=True,
+                     b_kmajor=False, lda=dcl.stride(0), ldb=self.D, ldc=self.D, epi_bwd=True, drop_p=ctx["p_c"],
+                     seed=ctx["sd_c"])
+        if dec_on:
+            self.decoder_bwd(ctx["dctx"], ddl, ctx["enc"], denc, bt)
+        if enc_on:
+            self.encoder_bwd(ctx["ectx"], denc)
+        else:
+            self._encoder_bwd_end()
 
     # ========================================================================= inference
     def encode(self, audios, videos, video_lengths=None, train=False):

@@ -69,7 +69,13 @@ class GradReducer:
     compress="bf16" (off by default: fp32 keeps gradient parity with the reference's DDP)
     halves the bytes on xGMI: a bucket is cast to bf16 on the comm stream, summed in bf16 by
     RCCL and cast back into the fp32 arena (torch DDP's bf16_compress_hook, minus its
-    pre-division: the 1/world factor stays in the optimizer or finish(average=True))."""
+    pre-division: the 1/world factor stays in the optimizer or finish(average=True)).
+
+    written (None: everything): the [start, end) ranges some backward wrote since the last gradient
+    clear (Arena.written_ranges: the rest belongs to parameters frozen with requires_grad=False).
+    A bucket that meets none of them is not exchanged, neither by ready() nor by finish(). As for
+    torch DDP, the frozen set must be the same on every rank: a rank that skips a bucket another
+    rank sends would hang the collective."""
 
     def __init__(self, flat_grad, bucket_bytes=BUCKET_BYTES, group=None, use_stream=True, segment=None,
                  compress=None):
@@ -100,6 +106,8 @@ class GradReducer:
         self._next = 0
         self._works = []
         self.enabled = True          # False inside ArenaDDP.no_sync(): gradients accumulate locally
+        self.written = None          # ranges with a gradient (None: all); see the class docstring
+        self.skipped = 0             # buckets left out since begin()
         self.extra_streams = []      # other streams that produce gradients (the engine's side stream)
         # optional timing (bench.py): per reduced step, HIP events (comm start, comm end) on
         # the comm stream and (backward end, join) on the compute stream — join - backward
@@ -121,6 +129,10 @@ class GradReducer:
             _cast(self.cbuf[a:b], self.flat[a:b])
 
     def _launch(self, ranges):
+        if self.written is not None:
+            keep = [(a, b) for a, b in ranges if any(s < b and a < e for s, e in self.written)]
+            self.skipped += len(ranges) - len(keep)
+            ranges = keep
         if not ranges:
             return
         if self.stream is None:
@@ -142,6 +154,7 @@ class GradReducer:
         self._next = 0
         self._works = []
         self._t0 = None
+        self.skipped = 0
 
     def ready(self, offset):
         """the decay segment is final from `offset` on: reduce every bucket inside it"""
@@ -208,6 +221,9 @@ class ArenaDDP:
             model(**mb).loss.backward()
         model(**mb_last).loss.backward()        # all-reduce overlapped with this backward
 
+    Parameters frozen with requires_grad=False must be the same on every rank (torch DDP's
+    condition too): buckets that lie wholly in ranges no backward wrote are not exchanged.
+
     average=True divides the summed gradients by the world size (DDP); average=False leaves
     the 1/world factor to FusedAdamW.step(grad_scale=1/world) and saves one pass."""
 
@@ -243,6 +259,10 @@ class ArenaDDP:
         self.require_forward_param_sync = self.require_backward_grad_sync
 
     def _pre_backward(self):
+        # (the engine has recorded this backward's frozen parameters in the arena by now; under
+        # no_sync() accumulation a range any micro-step wrote is exchanged)
+        written = getattr(self.eng.arena, "written_ranges", None)    # (absent on a bare gradient holder)
+        self.reducer.written = written() if written is not None else None
         self.reducer.enabled = self.require_backward_grad_sync
         self.reducer.begin()
 

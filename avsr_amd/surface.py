@@ -61,10 +61,11 @@ class _EncoderStep(torch.autograd.Function):
     backward = Engine.encoder_bwd (weight gradients land in the arena)."""
 
     @staticmethod
-    def forward(fctx, anchor, eng, audios, videos, bt, seeds, modality):
+    def forward(fctx, anchor, eng, audios, videos, bt, seeds, modality, snap):
         if eng.before_forward is not None:      # DDP buffer broadcast (parallel.ArenaDDP)
             eng.before_forward()
-        x, ctx = eng.encoder_fwd(audios, videos, bt, True, True, seeds, modality)
+        x, ctx = eng.encoder_fwd(audios, videos, bt, True, True, seeds, modality, plan=eng._plan(snap))
+        ctx["snap"] = snap
         fctx.eng, fctx.ctx = eng, ctx
         B, T = bt["B"], bt["T"]
         out = torch.empty(B, T, eng.D, device=eng.device, dtype=torch.float32)
@@ -74,12 +75,12 @@ class _EncoderStep(torch.autograd.Function):
     @staticmethod
     def backward(fctx, dout):
         eng = fctx.eng
-        eng.arena.attach_grads()
+        eng.arena.attach_grads(snap=fctx.ctx["snap"])
         B, T, D = dout.shape
         d = to_engine(eng, dout.reshape(B * T, D), eng.dtype)
         eng.encoder_backward(fctx.ctx, d)     # with the DDP reducer's begin / buckets / finish
         fctx.ctx = None
-        return (None,) * 7
+        return (None,) * 8
 
 
 def encoder_forward(e2e, input_features, attention_mask=None, video=None, **kwargs):
@@ -91,10 +92,13 @@ def encoder_forward(e2e, input_features, attention_mask=None, video=None, **kwar
     B, _, T = video.shape[:3]
     lens = lengths_from_mask(attention_mask, B, T)
     train = e2e.encoder.training
-    if train and torch.is_grad_enabled():
+    # the backward follows this snapshot of the trainable parameters; with the whole encoder frozen
+    # (requires_grad=False) there is no graph
+    snap = eng.trainable() if train and torch.is_grad_enabled() else None
+    if snap is not None and (snap.all or eng._plan(snap).enc):
         bt = eng.prepare(video, input_features, lens)
         x = _EncoderStep.apply(e2e._anchor, eng, input_features.to(eng.device), video.to(eng.device), bt,
-                               eng.new_seeds(), eng.draw_modality(train=True))
+                               eng.new_seeds(), eng.draw_modality(train=True), snap)
     else:
         x = to_engine(eng, eng.encode(input_features, video, lens, train=train), torch.float32)
     return BaseModelOutput(last_hidden_state=x, hidden_states=None, attentions=None)
