@@ -361,7 +361,7 @@ def check(rc, op):
 # kernel-selection options (avsr_hip.h AVSR_OPT_*, AVSR_TILE_*): A/B tools and variant tests
 OPTIONS = {"gemm_tile": 0, "attn_sq_fwd": 1, "attn_sq_bwd": 2, "wgrad_dual": 3, "conv_192": 4, "conv_s2phase": 5,
            "conv_patch": 6, "conv_wpatch": 7, "stem_pool_2x2": 8,
-           "stem_wpatch": 9}
+           "stem_wpatch": 9, "attn_enc_fused": 10}
 TILES = ["128", "256", "256x128", "128x256", "128s3", "128w8s3", "pp", "192", "192x256", "192w8s3", "64", "64s4"]
 ATTN_PATHS = ["f32", "tiled", "resident", "sq", "enc"]      # AVSR_ATTN_PATH_* in id order (avsr_attn_path)
 

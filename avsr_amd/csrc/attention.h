@@ -173,7 +173,7 @@ AVSR_DEV void stamp(int slot) {
   }
 }
 // the same per workgroup for a 1-D grid at buffer offset `part` x (6 x gridDim.x): the encoder
-// backward's dQ (part 0) and dK / dV (part 1) kernels
+// backward's fused kernel (part 0), or its dQ (part 0) and dK / dV (part 1) kernels
 AVSR_DEV void stamp_part(int slot, int part) {
   unsigned long long* st = g_stamps;
   if (st != nullptr && threadIdx.x == 0) {

@@ -136,7 +136,7 @@ extern "C" int avsr_attn_dropmask(const avsr_attn_params* p, void* stream) {
 }
 
 // only the F32 and TILED backward read a precomputed delta: the encoder backward computes it in
-// its dQ kernel, the resident backward inside its dK/dV kernel
+// its prologue (fused kernel) or its dQ kernel, the resident backward inside its dK/dV kernel
 extern "C" int avsr_attn_bwd_prep(const avsr_attn_params* p, void* stream) {
   int rc = check(p);
   if (rc) return rc;

@@ -246,6 +246,8 @@ __global__ __launch_bounds__(256, 3) void attn_fwd_kernel(AttnArgs a, int nqb) {
 //     (K fragments re-read per tile instead of held: the register file then holds dK, dV,
 //     V and the tile without spilling at 3 waves per SIMD).
 // DM: 0 no dropout, 1 hashed per element (AttnDrop), 2 stored keep masks (a.mq).
+// These two kernels are the path of option attn_enc_fused = 0; the default is the one fused
+// kernel further down (attn_bwd_kernel), which is tested against them.
 namespace rb {
 using sq::swz; using sq::rsrc; using sq::dma16; using sq::dma4; using sq::vmwait;   // the DMA pieces
 using sq::FragOff; using sq::ldA; using sq::ldT;                                    // the swizzled fragments
@@ -540,12 +542,304 @@ __global__ __launch_bounds__(NTH) void attn_bwd_dkdv_kernel(AttnArgs a) {
   }
 }
 
+// ---- the fused backward: dQ from the dK / dV pass (option attn_enc_fused) -----------------
+// The dK / dV kernel's walk (wave w owns key block w; dK, dV and the V fragments in registers;
+// query tiles in order) with three additions. (1) The prologue computes delta for queries
+// 32w.. as the dQ kernel does and publishes it in LDS (and in a.delta). (2) Q / dO go through a
+// two-slot ring of the 96-row DMA rounds instead of resident images: round r + 2 is issued after
+// the barrier that ends round r, round r + 1 lands while r computes. (3) Every active wave
+// leaves its bf16 dS tile [key][query] in a double-buffered exchange; after the tile's one
+// barrier two rotating waves (one per 32-column half of dh) form dQ_t = sum_w dS[t, w] K_w from
+// the exchange and the K image, keys ascending in one accumulator chain, and store it.
+// Every wave executes every barrier and every counted wait: those sit outside all conditions on
+// w, klen, Lq and `active` (the tile loop always runs its 12 steps).
+// LDS (bytes): ring 2 x (Q 12 K | dO 12 K) | K image 48 K | lse, delta 3 K | exchange 2 x 24 K |
+// two dQ store slabs [32][33] floats = 155.25 KiB; the dK / dV store slabs reuse it from 0.
+constexpr int RROWS = NTH / 64 * 8;                 // rows of one DMA round: an 8-row piece per wave
+constexpr int RIMG = RROWS * 128;                   // one operand's image of a round
+constexpr int SLOTB = 2 * RIMG;                     // ring slot: Q | dO
+constexpr int XTILE = 32 * 64;                      // one wave's dS tile: [32 keys][32 queries] bf16
+constexpr int XBUF = NTH / 64 * XTILE;
+constexpr int DQSLAB = 32 * 33 * 4;
+constexpr int F_K = 2 * SLOTB, F_LSE = F_K + IMG384, F_X = F_LSE + 2 * MAXR * 4, F_ST = F_X + 2 * XBUF;
+constexpr size_t FUSED_LDS = F_ST + 2 * DQSLAB;
+static_assert(MAXR == 4 * RROWS && RROWS % 32 == 0 && RROWS % 16 == 0, "four rounds of whole tiles, swizzle period 16");
+static_assert(FUSED_LDS <= 160 * 1024 && NTH / 64 * 32 * 65 * 4 <= FUSED_LDS, "fused backward LDS");
+static_assert(F_X % 16 == 0 && F_ST % 16 == 0, "exchange / slab alignment");
+
+// The ring's DMA: wave w moves the 8-row piece w of each round. The round's rows 96 r .. go into
+// the descriptor (base and extent, scalar), so the per-lane offset is the same every round;
+// rows past n lie outside the extent and land as zeros (swz(96 r + x) = swz(x))
+AVSR_DEV uint32_t round_voff(int64_t ld, int w, int l) {
+  const int row = 8 * w + (l >> 3), ch = (l & 7) ^ swz(row);
+  return (uint32_t)((row * ld + ch * 8) * 2);
+}
+AVSR_DEV void dma_round(const bf16* base, int64_t ld, int n, char* img, int r, uint32_t voff, int w) {
+  const int nr = n - RROWS * r;
+  dma16(rsrc(base + (int64_t)RROWS * r * ld, nr > 0 ? (uint32_t)(((nr - 1) * ld + DH) * 2) : 0u), voff, img + w * 1024);
+}
+
+// The exchange tile of a wave: row = key (64 B), 8-byte chunk j = queries 4j..4j+3 at position
+// j ^ (key >> 2): the writers (key on the lane, one chunk j each: without the xor keys 4 apart
+// would share a bank) spread evenly over the banks, and the transposed readers
+// (ds_read_b64_tr_b16) read whole rows, 256 contiguous bytes per half-wave.
+AVSR_DEV uint32_t xoff(int key, int j) { return (uint32_t)(key * 64 + ((j ^ ((key >> 2) & 7)) << 3)); }
+
+// dQ_t columns 32 cb .. 32 cb + 31 by one wave: acc[r] = dQ^T[d = 32 cb + qrow(r, hh)][query c]
+// (the dQ kernel's form: A = K^T fragments of the image, B = dS with the query on the lane),
+// then through the wave's slab to whole 64-byte (bf16) / 128-byte (fp32) row halves of `out`
+template <typename OutT>
+AVSR_DEV void dq_tile(const char* X, const char* Ks, int nkb, int cb, const FragOff& fo, int l, float scale,
+                      float* slab, OutT* out, int64_t ld, int nvalid) {
+  // opaque per call: the per-lane offsets below are recomputed for every tile instead of staying
+  // live (shared by the 12 unrolled tiles) across the dK / dV register peak
+  asm volatile("" : "+v"(l));
+  const int c = l & 31, hh = l >> 5, g = (l >> 4) & 1, i = l & 15;
+  const uint32_t kt0 = cb ? fo.tr[1][0] : fo.tr[0][0], kt1 = cb ? fo.tr[1][1] : fo.tr[0][1];
+  uint32_t xo[2][2];                                   // keys 16 S + 8 e + 4 hh + 0..3, query c
+#pragma unroll
+  for (int S = 0; S < 2; ++S)
+#pragma unroll
+    for (int e = 0; e < 2; ++e) xo[S][e] = xoff(16 * S + 8 * e + 4 * hh + (i >> 2), 4 * g + (i & 3));
+  f32x16 acc;
+  zacc(acc);
+  // the fragments of key block kb + 1 are read while block kb multiplies (the last step re-reads
+  // its own block: no branch); one chain, so the sum runs over the keys in ascending order
+  union Frag { s4v s[2]; bf16x8 x; } ka[2], ds[2];
+  auto read = [&](int kb) {
+    const char* Kb = Ks + kb * 4096;
+    const char* Xb = X + kb * XTILE;
+#pragma unroll
+    for (int S = 0; S < 2; ++S) {
+      ka[S].s[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(Kb + S * 2048 + kt0));
+      ka[S].s[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(Kb + S * 2048 + kt1));
+      ds[S].s[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(Xb + xo[S][0]));
+      ds[S].s[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4v*)(Xb + xo[S][1]));
+    }
+  };
+  read(0);
+  for (int kb = 0; kb < nkb; ++kb) {
+    const bf16x8 a0 = ka[0].x, b0 = ds[0].x, a1 = ka[1].x, b1 = ds[1].x;
+    read(min(kb + 1, nkb - 1));
+    acc = mfma32(a0, b0, acc);
+    acc = mfma32(a1, b1, acc);
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) slab[c * 33 + qrow(r, hh)] = acc[r] * scale;
+  __builtin_amdgcn_wave_barrier();       // the slab is this wave's own: LDS serves a wave in order
+  constexpr int VE = 16 / (int)sizeof(OutT), LPR = 32 / VE, RPI = 64 / LPR;
+  const int rr = l / LPR, ch = (l % LPR) * VE;
+#pragma unroll
+  for (int i0 = 0; i0 < 32; i0 += RPI) {
+    const int q = i0 + rr;
+    if (q < nvalid) {
+      float v[VE];
+#pragma unroll
+      for (int j = 0; j < VE; ++j) v[j] = slab[q * 33 + ch + j];
+      stv(out + (int64_t)q * ld + ch, v);
+    }
+  }
+}
+
+template <typename OutT, int DM>
+__global__ __launch_bounds__(NTH) void attn_bwd_kernel(AttnArgs a, OutT* dq, int64_t lddq) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Ks = smem + F_K;
+  float* lss = (float*)(smem + F_LSE);                     // lse, then lse * log2(e) (0 past Lq)
+  float* dls = lss + MAXR;                                 // delta (0 past Lq)
+  stamp_part(0, 0);
+  const int bh = xcd_id(blockIdx.x, gridDim.x), b = bh / a.H, h = bh % a.H;
+  const int tid = threadIdx.x, l = tid & 63, c = l & 31, hh = l >> 5;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const char* Kw = Ks + w * 4096;                          // this wave's 32 rows of the K image
+  const int kb0 = w * 32, key = kb0 + c;
+  const bf16* Qg = (const bf16*)a.q + (int64_t)b * a.Lq * a.ldq + h * DH;
+  const bf16* dOg = (const bf16*)a.dout + (int64_t)b * a.Lq * a.lddo + h * DH;
+  const bf16* Og = (const bf16*)a.o + (int64_t)b * a.Lq * a.ldo + h * DH;
+  const bf16* Kg = (const bf16*)a.k + ((int64_t)b * a.Lk + kb0) * a.ldk + h * DH;
+  const bf16* V = (const bf16*)a.v + (int64_t)b * a.Lk * a.ldv + h * DH;
+  // this wave's K rows (4 pieces; rows past Lk zero), round 0 of Q / dO, the lse rows
+  if (kb0 < a.Lk) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dma_piece(Kg, a.ldk, min(32, a.Lk - kb0), Ks + w * 4096, i, l);
+  }
+  const uint32_t vq = round_voff(a.ldq, w, l), vdo = round_voff(a.lddo, w, l);
+  dma_round(Qg, a.ldq, a.Lq, smem, 0, vq, w);
+  dma_round(dOg, a.lddo, a.Lq, smem + RIMG, 0, vdo, w);
+  if (w < 6) dma4(rsrc(a.lse + (int64_t)bh * a.Lq, (uint32_t)(a.Lq * 4)), (uint32_t)((64 * w + l) * 4), (char*)(lss + 64 * w));
+  // V fragments of this wave's keys; delta of queries 32 w .. from this lane's dO / O half-rows,
+  // the dQ kernel's arithmetic (the two paths publish the same bits)
+  const int qi = kb0 + c;
+  const bool qok = qi < a.Lq;
+  bf16x8 vf[4];
+  float dsum = 0.f;
+  {
+    bf16x8 of[4], ov[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      vf[s] = ldrow_sel(V, a.ldv, key, a.Lk, s * 16 + 8 * hh);
+      of[s] = ldrow_sel(dOg, a.lddo, qi, a.Lq, s * 16 + 8 * hh);
+      ov[s] = ldrow_sel(Og, a.ldo, qi, a.Lq, s * 16 + 8 * hh);
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) asm volatile("" ::"v"(vf[s]), "v"(of[s]), "v"(ov[s]));
+    vmwait<0>();                                           // these loads, the K rows, round 0, lse
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dsum = fmaf((float)of[s][j], (float)ov[s][j], dsum);
+  }
+  dsum = xor32_sum(dsum);
+  if (hh == 0) {
+    if (qok) a.delta[(int64_t)bh * a.Lq + qi] = dsum;
+    dls[qi] = qok ? dsum : 0.f;
+  }
+  dma_round(Qg, a.ldq, a.Lq, smem + SLOTB, 1, vq, w);      // round 1 in flight from here on
+  dma_round(dOg, a.lddo, a.Lq, smem + SLOTB + RIMG, 1, vdo, w);
+  round_barrier();
+  if (tid < MAXR) lss[tid] *= LOG2E;
+  const int klen = a.klen ? min(a.klen[b], a.Lk) : a.Lk;
+  const bool active = kb0 < klen, kok = key < klen;
+  const int nkb = (klen + 31) >> 5;                        // key blocks that take part in dQ
+  const float sl2 = a.scale * LOG2E;
+  const AttnDrop drop(a.drop_p, a.seed, a.B, a.H, a.Lq, a.Lk);
+  const float dscale = DM ? drop.scale : 1.f;
+  const uint32_t nG = DM == 1 ? drop.npair * GOLD : 0u;
+  const uint32_t keyG = DM == 1 ? ((uint32_t)bh * (uint32_t)a.Lq * drop.npair + (uint32_t)(min(key, a.Lk - 1) >> 1)) * GOLD : 0u;
+  const bool odd = c & 1;
+  // DM 2: as the dK / dV kernel (one 8-byte load per lane per tile, the half for this key)
+  const uint64_t* mp = DM == 2 ? a.mq + ((int64_t)bh * a.mnqb * a.mnkb + w) * 16 + ((c & 3) + 4 * (c >> 3)) : nullptr;
+  const int mstride = a.mnkb * 16;
+  const bool mhi = (c >> 2) & 1;
+  const int nt = (a.Lq + 31) >> 5;
+  FragOff fo;
+  fo.init(l);
+  // this lane's chunk 0 (hh: 1) of its key's row in the wave's tile of exchange buffer 0; chunk
+  // 2i + hh of the row is this address with bits 4..5 xor i (xoff)
+  char* Xw = smem + F_X + w * XTILE;
+  const uint32_t xw = xoff(c, hh);
+  OutT* DQ = dq + (int64_t)b * a.Lq * lddq + h * DH;
+  f32x16 dv0, dv1, dk0, dk1;
+  zacc(dv0); zacc(dv1); zacc(dk0); zacc(dk1);
+  round_barrier();                                         // the lse scaling is visible
+  stamp_part(1, 0);
+#pragma unroll
+  for (int t = 0; t < MAXR / 32; ++t) {                    // unrolled: slot and tile offsets become immediates
+    const int r = t / 3, u = t % 3, qt0 = t * 32;
+    const char* Qs = smem + (r & 1) * SLOTB;
+    const char* dOs = Qs + RIMG;
+    if (active && t < nt) {
+      uint32_t mbits = 0;
+      if (DM == 2) {
+        const uint64_t m64 = mp[(int64_t)t * mstride];
+        mbits = (mhi ? (uint32_t)(m64 >> 32) : (uint32_t)m64) >> (4 * hh);
+      }
+      const char* Qt = Qs + u * 4096;
+      const char* dOt = dOs + u * 4096;
+      f32x16 sc, dp;
+      zacc(sc); zacc(dp);
+      // K fragments re-read every tile (see the dK / dV kernel)
+      uint32_t kz = 0;
+      asm volatile("" : "+v"(kz));
+      const char* Kt = Kw + kz;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        sc = mfma32(ldA(Qt, fo.row[s]), ldA(Kt, fo.row[s]), sc);
+        dp = mfma32(ldA(dOt, fo.row[s]), vf[s], dp);
+      }
+      if (!(kb0 + 32 <= klen && qt0 + 32 <= a.Lq)) {       // wave-uniform: invalid keys / queries
+#pragma unroll
+        for (int e = 0; e < 16; ++e) sc[e] = kok & (qt0 + qrow(e, hh) < a.Lq) ? sc[e] : -INFINITY;
+      }
+      const uint32_t tG = keyG + (uint32_t)(qt0 + 4 * hh) * nG;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {                        // registers 4i..4i+3 = queries qt0 + 8i + 4hh + 0..3
+        const f32x4 ls = *(const f32x4*)&lss[qt0 + 8 * i + 4 * hh];
+        const f32x4 ds = *(const f32x4*)&dls[qt0 + 8 * i + 4 * hh];
+        bool kb[4] = {true, true, true, true};
+        if (DM == 1) {
+#pragma unroll
+          for (int u2 = 0; u2 < 2; ++u2) {
+            const uint32_t mine = hashG(tG + (uint32_t)(8 * i + (odd ? 2 : 0) + u2) * nG, drop.pre);
+            const uint32_t other = __shfl_xor(mine, 1, 64);
+            const uint32_t h0 = odd ? other : mine, h1 = odd ? mine : other;
+            kb[u2] = (odd ? (h0 >> 16) : (h0 & 0xFFFFu)) >= drop.thr;
+            kb[u2 + 2] = (odd ? (h1 >> 16) : (h1 & 0xFFFFu)) >= drop.thr;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r4 = 4 * i + e;
+          const float p = fexp2(fmaf(sc[r4], sl2, -ls[e]));
+          if (DM == 2) {
+            const bool kp = (mbits >> ((r4 & 3) + 8 * (r4 >> 2))) & 1u;
+            sc[r4] = kp ? p : 0.f;
+            dp[r4] = p * fmaf(kp ? dp[r4] : 0.f, dscale, -ds[e]);
+          } else {
+            sc[r4] = kb[e] ? p : 0.f;
+            dp[r4] = p * fmaf(kb[e] ? dp[r4] : 0.f, dscale, -ds[e]);
+          }
+        }
+      }
+      const bf16x8 pa = accb(sc, 0), pb = accb(sc, 1), sa = accb(dp, 0), sb = accb(dp, 1);
+      // dS[queries 4j..4j+3][key c], j = 2i + hh, for the dQ waves
+      char* Xt = Xw + (t & 1) * XBUF;
+      *(bf16x4*)(Xt + xw) = __builtin_shufflevector(sa, sa, 0, 1, 2, 3);
+      *(bf16x4*)(Xt + (xw ^ 16u)) = __builtin_shufflevector(sa, sa, 4, 5, 6, 7);
+      *(bf16x4*)(Xt + (xw ^ 32u)) = __builtin_shufflevector(sb, sb, 0, 1, 2, 3);
+      *(bf16x4*)(Xt + (xw ^ 48u)) = __builtin_shufflevector(sb, sb, 4, 5, 6, 7);
+      dv0 = mfma32(ldT(dOs, 32 * u, fo, 0), pa, dv0);
+      dv0 = mfma32(ldT(dOs, 32 * u + 16, fo, 0), pb, dv0);
+      dv1 = mfma32(ldT(dOs, 32 * u, fo, 1), pa, dv1);
+      dv1 = mfma32(ldT(dOs, 32 * u + 16, fo, 1), pb, dv1);
+      dk0 = mfma32(ldT(Qs, 32 * u, fo, 0), sa, dk0);
+      dk0 = mfma32(ldT(Qs, 32 * u + 16, fo, 0), sb, dk0);
+      dk1 = mfma32(ldT(Qs, 32 * u, fo, 1), sa, dk1);
+      dk1 = mfma32(ldT(Qs, 32 * u + 16, fo, 1), sb, dk1);
+    }
+    if (u == 2) vmwait<0>();               // this wave's pieces of round r + 1 have landed
+    round_barrier();                       // tile t's dS is complete; every wave is done with Q / dO tile t
+    if (u == 2 && r + 2 < 4) {             // the slot of round r is free
+      dma_round(Qg, a.ldq, a.Lq, smem + (r & 1) * SLOTB, r + 2, vq, w);
+      dma_round(dOg, a.lddo, a.Lq, smem + (r & 1) * SLOTB + RIMG, r + 2, vdo, w);
+    }
+    const int cb = w - (2 * t) % (NTH / 64);               // the tile's two dQ waves rotate
+    if (t < nt && (cb == 0 || cb == 1))
+      dq_tile<OutT>(smem + F_X + (t & 1) * XBUF, Ks, nkb, cb, fo, l, a.scale, (float*)(smem + F_ST + cb * DQSLAB),
+                    DQ + (int64_t)qt0 * lddq + 32 * cb, lddq, a.Lq - qt0);
+  }
+  stamp_part(2, 0);
+  __syncthreads();                         // the last dQ waves are done: everything is store slabs now
+  {
+    float* scr = (float*)smem + w * 32 * 65;
+    bf16* DK = (bf16*)a.dk + ((int64_t)b * a.Lk + kb0) * a.lddk + h * DH;
+    store_t<bf16>(dk0, dk1, a.scale, scr, DK, a.lddk, a.Lk - kb0);     // waves past Lk: no valid row
+    bf16* DV = (bf16*)a.dv + ((int64_t)b * a.Lk + kb0) * a.lddv + h * DH;
+    store_t<bf16>(dv0, dv1, dscale, scr, DV, a.lddv, a.Lk - kb0);
+  }
+  if (g_stamps != nullptr) {
+    __syncthreads();
+    stamp_part(3, 0);
+  }
+}
+
 constexpr size_t DQ_LDS = 2 * IMG384 > NTH / 64 * 32 * 65 * 4 ? 2 * IMG384 : NTH / 64 * 32 * 65 * 4;
 constexpr size_t DKDV_LDS = 3 * IMG384 + 2 * MAXR * 4;
 static_assert(DKDV_LDS <= 160 * 1024 && NTH / 64 * 32 * 65 * 4 <= DKDV_LDS, "dK/dV LDS");
 
+// AVSR_OPT_ATTN_ENC_FUSED = 1: the one-kernel backward; 0: the dQ kernel, then the dK / dV kernel
 template <int DM> void launch(const avsr_attn_params* p, const AttnArgs& a, hipStream_t st) {
   const dim3 g(p->B * p->H);
+  if (avsr_opt(AVSR_OPT_ATTN_ENC_FUSED) != 0) {
+    if (p->dq_out) {
+      allow_lds(attn_bwd_kernel<bf16, DM>);
+      hipLaunchKernelGGL((attn_bwd_kernel<bf16, DM>), g, dim3(NTH), FUSED_LDS, st, a, (bf16*)p->dq_out, p->lddq_out);
+    } else {
+      allow_lds(attn_bwd_kernel<float, DM>);
+      hipLaunchKernelGGL((attn_bwd_kernel<float, DM>), g, dim3(NTH), FUSED_LDS, st, a, p->dq, p->lddq);
+    }
+    return;
+  }
   if (p->dq_out) {
     allow_lds(attn_bwd_dq_kernel<bf16, DM>);
     hipLaunchKernelGGL((attn_bwd_dq_kernel<bf16, DM>), g, dim3(NTH), DQ_LDS, st, a, (bf16*)p->dq_out, p->lddq_out);

@@ -5,9 +5,13 @@
 
 extern "C" const char* avsr_version(void) { return "avsr_hip 0.2.0 gfx950"; }
 
+#ifndef AVSR_AB_ATTN_ENC_FUSED   // A/B builds only (tools/build_variant.py): the default of attn_enc_fused
+#define AVSR_AB_ATTN_ENC_FUSED 1
+#endif
+
 namespace {
 // defaults = the production choices documented in avsr_hip.h
-std::atomic<int64_t> g_opt[AVSR_OPT_COUNT] = {{0}, {1}, {0}, {1}, {1}, {1}, {1}, {1}, {1}, {1}};
+std::atomic<int64_t> g_opt[AVSR_OPT_COUNT] = {{0}, {1}, {0}, {1}, {1}, {1}, {1}, {1}, {1}, {1}, {AVSR_AB_ATTN_ENC_FUSED}};
 
 bool opt_valid(int option, int64_t v) {
   switch (option) {
@@ -20,7 +24,8 @@ bool opt_valid(int option, int64_t v) {
     case AVSR_OPT_CONV_PATCH:
     case AVSR_OPT_CONV_WPATCH:
     case AVSR_OPT_STEM_POOL_2X2:
-    case AVSR_OPT_STEM_WPATCH: return v == 0 || v == 1;
+    case AVSR_OPT_STEM_WPATCH:
+    case AVSR_OPT_ATTN_ENC_FUSED: return v == 0 || v == 1;
     default: return false;
   }
 }

@@ -61,6 +61,9 @@ const char* avsr_version(void);
  *   AVSR_OPT_STEM_WPATCH    [1]  1: patch-resident stem weight-grad (packed 8-channel input,
  *                                 7x7 / stride 2); 0: the general split-K weight-grad (fp32
  *                                 re-association)
+ *   AVSR_OPT_ATTN_ENC_FUSED [1]  1: encoder attention backward in one kernel (dQ from the
+ *                                 dK / dV pass); 0: the dQ kernel, then the dK / dV kernel
+ *                                 (dK, dV, delta bit-identical; dQ within one rounding of dS)
  * avsr_set_option returns 0, or AVSR_E_ARG for an unknown option or a value out of range;
  * avsr_get_option returns the value, or -1 for an unknown option.
  * ------------------------------------------------------------------------------------ */
@@ -75,7 +78,8 @@ enum {
   AVSR_OPT_CONV_WPATCH = 7,
   AVSR_OPT_STEM_POOL_2X2 = 8,
   AVSR_OPT_STEM_WPATCH = 9,
-  AVSR_OPT_COUNT = 10
+  AVSR_OPT_ATTN_ENC_FUSED = 10,
+  AVSR_OPT_COUNT = 11
 };
 /* tile configurations of the bf16 GEMM core (AVSR_OPT_GEMM_TILE = k + 1): rows x columns, wN =
  * N waves, sN = N LDS stages, PP = the 256x256 ping-pong core. One row each in gemm.hip's tile

@@ -1,7 +1,8 @@
 """Per-workgroup timelines (diagnostic) at C2 from in-kernel s_memrealtime stamps (100 MHz):
 start / first round landed / compute done / end, for the resident attention forward (`fwd`) or
-the encoder backward's dQ and dK / dV kernels (`bwd`, stored dropout mask). Prints launch span,
-median phase durations and workgroups per CU. usage: python tools/attn_stamps.py fwd|bwd [out.json]"""
+the encoder backward (`bwd`, stored dropout mask): its one kernel, or with the attn_enc_fused
+option at 0 (`bwd0`) the dQ and dK / dV kernels. Prints launch span,
+median phase durations and workgroups per CU. usage: python tools/attn_stamps.py fwd|bwd|bwd0 [out.json]"""
 import ctypes
 import json
 import os
@@ -25,7 +26,9 @@ lse = torch.empty(B * H * Lq, device=dev)
 delta = torch.empty(B * H * Lq, device=dev)
 klen = torch.full((B,), Lq, device=dev, dtype=torch.int32)
 mask = torch.empty(ops.attn_mask_words(B, H, Lq, Lq), device=dev, dtype=torch.int64)
-parts = 1 if mode == "fwd" else 2
+if mode == "bwd0":
+    L.set_option("attn_enc_fused", 0)
+parts = 1 if mode == "fwd" or L.get_option("attn_enc_fused") else 2
 buf = torch.zeros(parts * B * H * 6, dtype=torch.int64, device=dev)
 lib = L.load()
 
