@@ -145,6 +145,14 @@ class CtcAlignParams(ctypes.Structure):
     ]
 
 
+class CtcBeamParams(ctypes.Structure):
+    _fields_ = [
+        ("U", _i), ("Tm", _i), ("V", _i), ("N", _i), ("C", _i), ("blank", _i), ("eos", _i), ("Lcap", _i),
+        ("logp", _c_p), ("ldp", _i64), ("tlen", _c_p), ("cand", _c_p), ("ws", _c_p),
+        ("n_out", _c_p), ("tokens", _c_p), ("len", _c_p), ("score", _c_p),
+    ]
+
+
 class EwParams(ctypes.Structure):
     _fields_ = [
         ("dtype", _i), ("rows", _i), ("N", _i), ("dy", _c_p), ("lddy", _i64), ("out", _c_p), ("ldout", _i64),
@@ -289,6 +297,7 @@ SYMBOLS = {
     "avsr_ctc_fwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_bwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_align": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
+    "avsr_ctc_beam": ([ctypes.POINTER(CtcBeamParams), _c_p], _i),
     "avsr_loss_finalize": ([_i, _c_p, _i, _c_p, _c_p, _f, _i, _c_p, _c_p], _i),
     "avsr_ew_bwd": ([ctypes.POINTER(EwParams), _c_p], _i),
     "avsr_colsum_defer": ([_i], _i),

@@ -17,6 +17,7 @@ from transformers.utils import ModelOutput
 from .configuration_avhubert_avsr import AVHubertAVSRConfig
 from .decode import BatchBeamSearch, Hypothesis, get_beam_search_decoder  # noqa: F401  (reference surface)
 from .nets.modules import E2EShell
+from .rescore import CTCRescoringSearch, get_rescoring_decoder  # noqa: F401  (two-pass decoding)
 
 
 @dataclass

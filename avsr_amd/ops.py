@@ -696,6 +696,59 @@ def ctc_align(x, B, T, V, labels, label_len, in_len, lse, *, blank=0, ali=None, 
     return ali, score, feasible
 
 
+def token_logp(x, V, target, out=None, lse=None):
+    """out[row] = float(x[row][target[row]]) - lse[row] in fp32, 0 where target[row] = -1: the
+    log-probability of each row's target under softmax(x[row][:V]) (x fp32 or bf16, target int32).
+    This is avsr_lsm_fwd at smoothing 0, negated: with e = 0 and conf = 1 its row loss is
+    (0 + 1*log 1) + lse - (0*(sum x - xt) + 1*xt) = lse - xt, every term of it exact (the kernel
+    skips the q*log q term of a zero q), and fp32 subtraction is antisymmetric, so the negation is
+    bit for bit float(xt) - lse. One launch, which also computes the row's lse."""
+    rows = x.shape[0]
+    if out is None:
+        out = torch.empty(rows, device=x.device, dtype=torch.float32)
+    if lse is None:
+        lse = torch.empty(rows, device=x.device, dtype=torch.float32)
+    lsm_fwd(x, V, target, 0.0, lse, out, None)
+    return out.neg_()
+
+
+CTC_BEAM_MAX = 16          # avsr_ctc_beam: beam and token beam
+CTC_BEAM_LCAP = 511        # longest prefix (avsr_ctc_fwd's 2L + 1 <= 1024)
+
+
+def ctc_beam_ws(U, Tm, N):
+    """bytes of prefix-tree workspace of ctc_beam (AVSR_CTC_BEAM_WS)"""
+    return U * (Tm * N + 1) * 8
+
+
+def ctc_beam(logp, tlen, cand, N, *, blank, eos, Lcap=None, ws=None):
+    """CTC prefix beam search (avsr_ctc_beam) of U utterances in one launch: logp (U, Tm, V) fp32
+    CTC log-probs, tlen (U,) int32 frames, cand (U, Tm, C) int32 candidate tokens per frame
+    (row_topk order). Returns device tensors n_out (U,) int32, tokens (U, N, Lcap) int32 (-1
+    padded), len (U, N) int32, score (U, N) fp32, best first. Lcap defaults to min(Tm, 511)."""
+    U, Tm, V = logp.shape
+    C = cand.shape[-1]
+    if logp.dtype != torch.float32 or cand.dtype != torch.int32 or tlen.dtype != torch.int32:
+        raise TypeError("ctc_beam: logp fp32, cand and tlen int32")
+    if logp.stride(2) != 1 or logp.stride(0) != Tm * logp.stride(1) or not cand.is_contiguous() \
+            or tuple(cand.shape[:2]) != (U, Tm) or tlen.numel() != U:
+        raise ValueError("ctc_beam: logp rows u*Tm + t, cand (U, Tm, C) contiguous, tlen (U,)")
+    if Lcap is None:
+        Lcap = min(Tm, CTC_BEAM_LCAP)
+    dev = logp.device
+    inside = 1 <= N <= CTC_BEAM_MAX and 0 <= Lcap <= CTC_BEAM_LCAP   # beyond: the launcher returns the shape error
+    n_out = torch.empty(U, device=dev, dtype=torch.int32)
+    tokens = torch.empty(U, N, Lcap, device=dev, dtype=torch.int32) if inside else None
+    length = torch.empty(U, N, device=dev, dtype=torch.int32) if inside else n_out
+    score = torch.empty(U, N, device=dev, dtype=torch.float32) if inside else n_out
+    if ws is None:
+        ws = torch.empty(max(1, ctc_beam_ws(U, Tm, N) // 8) if inside else 1, device=dev, dtype=torch.int64)
+    _call("avsr_ctc_beam", L.fill(L.CtcBeamParams, U=U, Tm=Tm, V=V, N=N, C=C, blank=blank, eos=eos, Lcap=Lcap,
+                                   logp=logp, ldp=logp.stride(1), tlen=tlen, cand=cand, ws=ws, n_out=n_out,
+                                   tokens=tokens, len=length, score=score))
+    return n_out, tokens, length, score
+
+
 def loss_finalize(B, nll, row_loss, row_correct, mtlalpha, out, att_per_token=False):
     """att_per_token: the attention loss divides by the number of target tokens
     (transformer_length_normalized_loss) instead of B"""

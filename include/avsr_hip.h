@@ -467,6 +467,10 @@ int avsr_attn_dropmask(const avsr_attn_params* p, void* stream);
  * avsr_lsm_fwd:   LabelSmoothingLoss rows (src/nets/backend/transformer/label_smoothing_loss.py
  *   :41-63, KL(q || softmax) with q = smoothing/(V-1) off-target, 1-smoothing on target,
  *   target -1 ignored) -> row_loss, and th_accuracy's argmax match (nets_utils.py:303-323)
+ *   At smoothing = 0 the row loss is exactly lse[row] - float(x[row][target[row]]) (e = 0 and
+ *   conf = 1: the q*log q terms are skipped or log 1, and 0 * (sum x - xt) is 0), 0 on ignored
+ *   rows: the negated log-probability of the target, which the rescoring pass of two-pass
+ *   decoding sums per hypothesis (ops.token_logp) — no separate kernel.
  * avsr_lsm_bwd:   dx = (*dloss * coef) * (softmax - q), 0 on ignored rows
  * avsr_ctc_fwd:   torch.nn.CTCLoss(blank=0, reduction none, zero_infinity=True) per utterance
  *   (ctc.py:64-81): log-space alpha and beta over the extended label sequence; nll[b] and the
@@ -542,6 +546,56 @@ typedef struct {
 } avsr_ctc_align_params;
 #define AVSR_CTC_ALIGN_WS(B, T, Lmax) (((int64_t)(B) * (T) * (2 * (int64_t)(Lmax) + 1) + 3) & ~(int64_t)3)
 int avsr_ctc_align(const avsr_ctc_align_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * avsr_ctc_beam: time-synchronous CTC prefix beam search (the first pass of two-pass decoding,
+ *   avsr_amd/rescore.py; the reference has no such search) of U utterances in one launch, over
+ *   fp32 CTC log-probs logp (rows u*Tm + t, ldp floats apart) and C candidate tokens per frame
+ *   cand[u][t][0..C) (avsr_row_topk / avsr_log_softmax_topk order). Defined as if `next` were a
+ *   dictionary keyed by the token string; a (+)= b is a = logaddexp(a, b), all in fp32:
+ *     beam = {(): pb = 0, pnb = -inf}
+ *     for t < tlen[u], for every prefix l of the beam in rank order, tot = logaddexp(pb, pnb):
+ *       next[l].pb (+)= tot + logp[t][blank]                (blank need not be in cand)
+ *       for each candidate c in column order, p = logp[t][c]; c == blank, c == eos (never a
+ *       CTC label) and c outside [0, V) are skipped:
+ *         c == last(l):  next[l].pnb (+)= pnb + p;  next[l + c].pnb (+)= pb + p
+ *         otherwise:     next[l + c].pnb (+)= tot + p
+ *         (no extension beyond Lcap tokens)
+ *       beam = the N entries of next with the largest logaddexp(pb, pnb); ties go to the entry
+ *       created first (parent rank ascending, stay before extend, candidate column ascending;
+ *       an entry that was already in the beam counts as created by its own stay)
+ *   Outputs, best first: n_out[u] <= N; len[u][r]; score[u][r] = logaddexp(pb, pnb);
+ *   tokens[u][r][0..len). Fill values: tokens -1 beyond len and for r >= n_out, len 0 and score
+ *   -inf for r >= n_out. tlen[u] <= 0 gives n_out[u] = 0; tlen[u] > Tm is read as Tm. Padding
+ *   frames (t >= tlen[u]) are never read. Utterances do not influence each other: one
+ *   workgroup each, and the result is a function of that utterance's inputs alone (selection by
+ *   rank counting, no atomics).
+ *   Identity of a prefix is (length, 64-bit hash of the token string), so equal strings merge
+ *   however they were reached: an extension that is already in the beam, and a prefix that left
+ *   the beam and is re-created while an old extension of it survived. Two different strings of
+ *   one length collide with probability 2^-64 per comparison, at most Tm * N * (N + N*C)
+ *   comparisons per utterance (< 1e-12 at Tm = 1000, N = C = 16); the strings are therefore not
+ *   compared token by token (that walk would cost a dependent chain of len global reads per
+ *   comparison, every frame).
+ *   ws: caller-owned prefix tree (parent node, token) of the kept extensions,
+ *   AVSR_CTC_BEAM_WS(U, Tm, N) BYTES, 8-byte aligned (AVSR_E_ALIGN otherwise); contents on entry
+ *   are irrelevant. Limits: 1 <= N <= 16, 1 <= C <= 16, 0 <= Lcap <= 511 (so that a returned
+ *   hypothesis fits avsr_ctc_fwd's 2L + 1 <= 1024), AVSR_E_SHAPE beyond them. No allocation,
+ *   no host sync.
+ * ------------------------------------------------------------------------------------ */
+typedef struct {
+  int U, Tm, V, N, C, blank, eos, Lcap;
+  const float* logp; int64_t ldp;      /* [U*Tm][ldp], V valid columns */
+  const int* tlen;                     /* [U] */
+  const int* cand;                     /* [U][Tm][C] */
+  void* ws;                            /* AVSR_CTC_BEAM_WS(U, Tm, N) bytes */
+  int* n_out;                          /* [U] */
+  int* tokens;                         /* [U][N][Lcap] */
+  int* len;                            /* [U][N] */
+  float* score;                        /* [U][N] */
+} avsr_ctc_beam_params;
+#define AVSR_CTC_BEAM_WS(U, Tm, N) ((int64_t)(U) * ((int64_t)(Tm) * (N) + 1) * 8)
+int avsr_ctc_beam(const avsr_ctc_beam_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Elementwise / data-movement kernels around the GEMMs.
