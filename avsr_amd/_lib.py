@@ -274,6 +274,7 @@ SYMBOLS = {
     "avsr_conv_stat_tiles": ([ctypes.POINTER(ConvParams)], _i),
     "avsr_conv_bnr_tiles": ([ctypes.POINTER(ConvParams)], _i),
     "avsr_conv_wgrad_ws": ([ctypes.POINTER(ConvParams)], _i64),
+    "avsr_conv_path": ([ctypes.POINTER(ConvParams), _i], _i),
     "avsr_layernorm_fwd": ([ctypes.POINTER(LayerNormParams), _c_p], _i),
     "avsr_layernorm_bwd": ([ctypes.POINTER(LayerNormParams), _c_p], _i),
     "avsr_bn_finalize": ([ctypes.POINTER(BnFinalizeParams), _c_p], _i),
@@ -373,6 +374,8 @@ OPTIONS = {"gemm_tile": 0, "attn_sq_fwd": 1, "attn_sq_bwd": 2, "wgrad_dual": 3, 
            "stem_wpatch": 9, "attn_enc_fused": 10}
 TILES = ["128", "256", "256x128", "128x256", "128s3", "128w8s3", "pp", "192", "192x256", "192w8s3", "64", "64s4"]
 ATTN_PATHS = ["f32", "tiled", "resident", "sq", "enc"]      # AVSR_ATTN_PATH_* in id order (avsr_attn_path)
+CONV_PATHS = ["reg", "glds", "patch", "s2", "wpatch", "stem_wpatch"]   # AVSR_CONV_PATH_* in id order (avsr_conv_path)
+CONV_PASSES = ["fwd", "dgrad", "wgrad"]                     # AVSR_CONV_FWD / _DGRAD / _WGRAD
 
 
 def set_option(name, value):

@@ -304,6 +304,21 @@ def conv_stat_tiles(g, dtype):
     return L.load().avsr_conv_stat_tiles(ctypes.byref(p))
 
 
+def conv_path(g, dtype, pass_, *, bias=False, act=L.ACT_NONE, preact=False, res=False, ws=False, splitk=0):
+    """avsr_conv_path: the kernel family (a name of _lib.CONV_PATHS) that conv_fwd ("fwd"), conv_bwd_data
+    ("dgrad") or conv_bwd_weight ("wgrad") runs for geometry g under the current options; host-only, no
+    tensors. dtype: a torch dtype or an AVSR_* code; the flags say which optional operands the call
+    would pass (the query reads only whether they are set) and the weight-grad's splitk."""
+    p = g.params(_DT.get(dtype, dtype))
+    p.act, p.splitk = act, splitk
+    for name, on in (("bias", bias), ("preact", preact), ("res", res), ("ws", ws)):
+        setattr(p, name, 16 if on else None)            # never dereferenced
+    rc = L.load().avsr_conv_path(ctypes.byref(p), L.CONV_PASSES.index(pass_))
+    if not 0 <= rc < len(L.CONV_PATHS):
+        L.check(rc, "avsr_conv_path")
+    return L.CONV_PATHS[rc]
+
+
 def conv_fwd(g, x, w, y, stats=None, bias=None, act=L.ACT_NONE, preact=None, res=None):
     """y[pix, co] = act(conv(x, w) + bias) + res; stats: fp32 [cout, tiles, 3] BN partials."""
     p = g.params(dtype_code(x))

@@ -54,8 +54,8 @@ const char* avsr_version(void);
  *                                 col2im GEMM over all taps (bit-identical)
  *   AVSR_OPT_CONV_PATCH     [1]  1: patch-resident 3x3 kernel for 64-channel stride-1 fwd /
  *                                 data-grad; 0: the general implicit GEMM (bit-identical)
- *   AVSR_OPT_CONV_WPATCH    [1]  1: patch-resident weight-grad (stage 1 / 2 geometries); 0:
- *                                 the general split-K weight-grad (fp32 re-association)
+ *   AVSR_OPT_CONV_WPATCH    [1]  1: patch-resident weight-grad (ResNet stage 1-4 geometries);
+ *                                 0: the general split-K weight-grad (fp32 re-association)
  *   AVSR_OPT_STEM_POOL_2X2  [1]  1: stem max-pool forward / backward apply over 2x2 output
  *                                 blocks; 0: one output pixel per thread (bit-identical)
  *   AVSR_OPT_STEM_WPATCH    [1]  1: patch-resident stem weight-grad (packed 8-channel input,
@@ -253,6 +253,25 @@ int avsr_conv_stat_tiles(const avsr_conv_params* p);
 int avsr_conv_bnr_tiles(const avsr_conv_params* p);
 /* fp32 workspace (floats) bwd_weight uses when p->ws is given (0: it needs none) */
 int64_t avsr_conv_wgrad_ws(const avsr_conv_params* p);
+/* the kernel family avsr_conv_fwd (pass = AVSR_CONV_FWD), avsr_conv_bwd_data (AVSR_CONV_DGRAD) or
+ * avsr_conv_bwd_weight (AVSR_CONV_WGRAD) runs for this call under the current options: an
+ * AVSR_CONV_PATH_* id, or the AVSR_E_* code the call returns for its geometry or dtype
+ * (AVSR_E_ARG: p NULL or no such pass). It reads what the call reads, so whether bias / act / res /
+ * preact (forward) and ws (weight-grad) are set, and splitk, count. The three size queries above
+ * follow the same choice. Host-only: dereferences no pointer of the struct and touches no device.
+ *   REG          fp32 storage: register-staged implicit GEMM
+ *   GLDS         bf16: LDS-DMA implicit GEMM
+ *   PATCH        bf16 3x3 / stride 1 / pad 1 with 64 channels on both sides, forward without an
+ *                epilogue beyond the BN statistics, or data-grad: the input patch resident in LDS
+ *   S2           bf16 stride-2 data-grad as four parity-class GLDS GEMMs (data-grad only)
+ *   WPATCH       bf16 weight-grad of the ResNet stage 1-4 geometries with a workspace
+ *   STEM_WPATCH  bf16 weight-grad of the stem geometry on the packed input with a workspace */
+enum { AVSR_CONV_FWD = 0, AVSR_CONV_DGRAD = 1, AVSR_CONV_WGRAD = 2 };
+enum {
+  AVSR_CONV_PATH_REG = 0, AVSR_CONV_PATH_GLDS = 1, AVSR_CONV_PATH_PATCH = 2, AVSR_CONV_PATH_S2 = 3,
+  AVSR_CONV_PATH_WPATCH = 4, AVSR_CONV_PATH_STEM_WPATCH = 5
+};
+int avsr_conv_path(const avsr_conv_params* p, int pass);
 
 /* ------------------------------------------------------------------------------------
  * LayerNorm over the last dim (rows of N), fp32 statistics.

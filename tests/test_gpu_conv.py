@@ -14,28 +14,32 @@ def _rel(a, b):
 
 
 CASES = [
-    # nimg, h, w, cin, cout, k, stride, pad
-    (6, 22, 22, 64, 64, 3, 1, 1),
-    (5, 22, 22, 64, 128, 3, 2, 1),
-    (5, 22, 22, 64, 128, 1, 2, 0),
-    (7, 6, 6, 256, 512, 3, 2, 1),
-    (5, 11, 11, 128, 256, 3, 2, 1),   # odd input: parity classes of unequal size
-    (5, 11, 11, 128, 256, 1, 2, 0),
-    (4, 3, 3, 512, 512, 3, 1, 1),
-    (3, 88, 88, 8, 64, 7, 2, 3),      # stem as 2-D conv over 8 packed channels
+    # nimg, h, w, cin, cout, k, stride, pad; the bf16 kernel families (ops.conv_path) of the forward,
+    # the data-grad and the weight-grad (fp32: the register-staged kernel throughout)
+    (6, 22, 22, 64, 64, 3, 1, 1, "patch patch wpatch"),
+    (5, 22, 22, 64, 128, 3, 2, 1, "glds s2 glds"),
+    (5, 22, 22, 64, 128, 1, 2, 0, "glds s2 glds"),
+    (7, 6, 6, 256, 512, 3, 2, 1, "glds s2 glds"),
+    (5, 11, 11, 128, 256, 3, 2, 1, "glds s2 glds"),   # odd input: parity classes of unequal size
+    (5, 11, 11, 128, 256, 1, 2, 0, "glds s2 glds"),
+    (4, 3, 3, 512, 512, 3, 1, 1, "glds glds wpatch"),
+    (3, 88, 88, 8, 64, 7, 2, 3, "glds s2 stem_wpatch"),      # stem as 2-D conv over 8 packed channels
+    (4, 6, 6, 128, 64, 3, 1, 1, "glds glds glds"),    # cin > cout: the data-grad's weight extent is cout x k x k x cin
 ]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("case", CASES)
 def test_conv2d(dev, dtype, case):
-    n, h, w, cin, cout, k, s, p = case
+    n, h, w, cin, cout, k, s, p, families = case
     g = torch.Generator().manual_seed(n * 100 + cin)
     x = torch.randn(n, cin, h, w, generator=g)
     wt = torch.randn(cout, cin, k, k, generator=g) * (cin * k * k) ** -0.5
     ref = F.conv2d(x.double(), wt.double(), stride=s, padding=p)
     ho, wo = ref.shape[2], ref.shape[3]
     geom = ops.ConvGeom(n, h, w, cin, cout, k, k, (s, s), (p, p))
+    want = families.split() if dtype == torch.bfloat16 else ["reg"] * 3
+    assert [ops.conv_path(geom, dtype, q, ws=True) for q in ("fwd", "dgrad", "wgrad")] == want
     xd = x.permute(0, 2, 3, 1).contiguous().to(dev, dtype)
     wd = wt.permute(0, 2, 3, 1).contiguous().to(dev, dtype)
     y = torch.empty(n, ho, wo, cout, device=dev, dtype=dtype)
@@ -141,7 +145,7 @@ S2_CASES = [(5, 22, 22, 64, 128, 3, 2, 1), (5, 11, 11, 128, 256, 3, 2, 1), (7, 6
 @pytest.mark.parametrize("beta", [0.0, 1.0])
 @pytest.mark.parametrize("case", S2_CASES)
 def test_stride2_dgrad_parity_classes_match_full(dev, case, beta, monkeypatch, lib_opt):
-    """The stride-2 data-grad split into input-pixel parity classes (conv.hip s2_launch) adds
+    """The stride-2 data-grad split into input-pixel parity classes (conv.hip s2_launch, AVSR_CONV_PATH_S2) adds
     the same non-zero products in the same order as the full col2im GEMM: bit-identical."""
     n, h, w, cin, cout, k, s, p = case
     g = torch.Generator().manual_seed(n * 7 + cin + k)
@@ -153,6 +157,7 @@ def test_stride2_dgrad_parity_classes_match_full(dev, case, beta, monkeypatch, l
     outs = []
     for mode in ("1", "0"):
         lib_opt("conv_s2phase", int(mode))
+        assert ops.conv_path(geom, bf, "dgrad") == ("s2" if mode == "1" else "glds")
         dx = old.clone()
         ops.conv_bwd_data(geom, dy, wd, dx, beta=beta)
         outs.append(dx)
@@ -242,12 +247,14 @@ def test_wgrad_patch_matches_general(dev, nimg, hw, c, monkeypatch, lib_opt):
     xd = x.permute(0, 2, 3, 1).contiguous().to(dev, torch.bfloat16)
     dy = dyt.permute(0, 2, 3, 1).contiguous().to(dev, torch.bfloat16)
     init = torch.randn(c, 3, 3, c, generator=g).to(dev)
+    assert ops.conv_path(geom, torch.bfloat16, "wgrad", ws=True) == "wpatch"
     dw1 = init.clone()
     ops.conv_bwd_weight(geom, xd, dy, dw1)
     dw1b = init.clone()
     ops.conv_bwd_weight(geom, xd, dy, dw1b)
     assert torch.equal(dw1, dw1b)
     lib_opt("conv_wpatch", 0)
+    assert ops.conv_path(geom, torch.bfloat16, "wgrad", ws=True) == "glds"
     dw2 = init.clone()
     ops.conv_bwd_weight(geom, xd, dy, dw2)
     assert _rel(dw1 - init, dw2 - init) < 1e-4
@@ -270,12 +277,14 @@ def test_stem_wgrad_patch_matches_general(dev, nimg, lib_opt):
     xd = x.to(dev, torch.bfloat16)
     dy = torch.randn(nimg * 44 * 44, 64, generator=g).to(dev, torch.bfloat16)
     init = torch.randn(64, 7, 7, 8, generator=g).to(dev)
+    assert ops.conv_path(geom, torch.bfloat16, "wgrad", ws=True) == "stem_wpatch"
     dw1 = init.clone()
     ops.conv_bwd_weight(geom, xd, dy, dw1)
     dw1b = init.clone()
     ops.conv_bwd_weight(geom, xd, dy, dw1b)
     assert torch.equal(dw1, dw1b)
     lib_opt("stem_wpatch", 0)
+    assert ops.conv_path(geom, torch.bfloat16, "wgrad", ws=True) == "glds"
     dw2 = init.clone()
     ops.conv_bwd_weight(geom, xd, dy, dw2)
     assert _rel(dw1 - init, dw2 - init) < 1e-4

@@ -111,6 +111,113 @@ def test_attn_path_table():
     assert L.load().avsr_attn_path(None, 0) == 1004
 
 
+_S1 = (6, 22, 22, 64, 64, 3, 1, 1)          # ResNet stage 1
+_S2D = (5, 22, 22, 64, 128, 3, 2, 1)        # stage 2's stride-2 entry
+_S4 = (4, 3, 3, 512, 512, 3, 1, 1)          # stage 4
+_STEM = (3, 88, 88, 8, 64, 7, 2, 3)         # the stem as a 2-D conv over 8 packed channels
+_POS = (3, 37, 1, 16, 16, 128, 1, 0)        # the grouped pos-conv (its ConvGeom keywords below)
+_POS_KW = dict(groups=16, pad=(64, 0), kw=1, hout=37, wout=1)
+# the patch kernel's span rule (conv.hip patch_ok) for 64 channels, H = W: 255 + 2 (255 // W + 1) +
+# 2 (W + 2) (255 // W^2 + 1) + 2 (W + 3) + 1 <= PATCH_ROWS = 384 gives 384 at W = 24 and 388 at W = 25
+CONV_PATH_TABLE = [
+    # geometry (nimg, h, w, cin, cout, k, stride, pad); keywords (dtype, options by name, geom = ConvGeom
+    # keywords, the rest flags of ops.conv_path); then (family, figure) of the forward, the data-grad and the
+    # weight-grad with a workspace (None: not asked). Figure: the row-tile height (of every parity class
+    # for s2); for a weight-grad on the general kernels the split-K slabs (1: no workspace).
+    (_S1, {}, ("patch", 256), ("patch", 256), ("wpatch", None)),
+    (_S1, dict(bias=True), ("glds", 256), None, None),
+    (_S1, dict(act=L.ACT_GELU), ("glds", 256), None, None),
+    (_S1, dict(res=True), ("glds", 256), None, None),
+    (_S1, dict(preact=True), ("glds", 256), None, None),
+    (_S1, dict(conv_patch=0), ("glds", 256), ("glds", 256), None),
+    (_S1, dict(conv_wpatch=0), None, None, ("glds", 3)),
+    (_S1, dict(ws=False), None, None, ("glds", None)),
+    ((2, 24, 24, 64, 64, 3, 1, 1), {}, ("patch", 256), ("patch", 256), ("glds", 2)),
+    ((2, 25, 25, 64, 64, 3, 1, 1), {}, ("glds", 256), ("glds", 256), ("glds", 2)),
+    ((6, 11, 11, 64, 64, 3, 1, 1), {}, ("glds", 256), ("glds", 256), ("glds", 1)),      # span 409
+    (_S2D, {}, ("glds", 128), ("s2", 256), ("glds", 1)),
+    (_S2D, dict(conv_s2phase=0), None, ("glds", 256), None),
+    ((2, 8, 8, 16, 32, 3, 2, 1), {}, ("glds", 256), ("glds", 256), ("glds", 1)),        # cout % 64 != 0
+    ((6000, 11, 11, 128, 128, 3, 1, 1), {}, ("glds", 192), ("glds", 192), ("wpatch", None)),
+    ((6000, 11, 11, 128, 128, 3, 1, 1), dict(conv_192=0), ("glds", 128), ("glds", 128), None),
+    (_S4, {}, ("glds", 64), ("glds", 64), ("wpatch", None)),
+    (_S4, dict(splitk=3), None, None, ("glds", 1)),
+    (_S4, dict(ws=False), None, None, ("glds", None)),
+    (_STEM, {}, ("glds", 256), ("s2", 256), ("stem_wpatch", None)),
+    (_STEM, dict(stem_wpatch=0), None, None, ("glds", 6)),
+    (_STEM, dict(ws=False), None, None, ("glds", None)),
+    (_POS, dict(geom=_POS_KW), ("glds", 256), ("glds", 256), ("glds", 1)),
+    (_S1, dict(dtype=L.AVSR_F32), ("reg", 256), ("reg", 256), ("reg", 3)),
+    (_S2D, dict(dtype=L.AVSR_F32), ("reg", 128), ("reg", 256), ("reg", 1)),
+    (_S4, dict(dtype=L.AVSR_F32), ("reg", 64), ("reg", 64), ("reg", 1)),
+]
+
+
+def _conv_geom(case, **kw):
+    from avsr_amd import ops
+    n, h, w, cin, cout, k, s, p = case
+    return ops.ConvGeom(n, h, w, cin, cout, k, kw.pop("kw", k), kw.pop("stride", (s, s)), kw.pop("pad", (p, p)), **kw)
+
+
+def test_conv_path_table():
+    """avsr_conv_path: which kernel family a convolution runs per pass, on both sides of every
+    threshold of the choice (the forward epilogue flags, each conv_* option, the PATCH_ROWS span,
+    cout % 64 of the parity classes, the 192-row rule, a workspace and splitk for the weight-grad,
+    fp32), and the codes of a rejected call. The three size queries a caller allocates by must give
+    what the family and its tile imply: 256-row tiles for patch, the sum over the parity classes,
+    128 x 64 x 576 floats for wpatch, 256 x 64 x 392 for stem_wpatch, the slabs of a general
+    weight-grad. Host-side queries, no GPU."""
+    import pytest
+    from avsr_amd import ops
+    lib = L.load()
+    for case, kw, *passes in CONV_PATH_TABLE:
+        kw = dict(kw)
+        dtype = kw.pop("dtype", L.AVSR_BF16)
+        g = _conv_geom(case, **kw.pop("geom", {}))
+        opts = {k: kw.pop(k) for k in list(kw) if k in L.OPTIONS}
+        prev = {k: L.set_option(k, v) for k, v in opts.items()}
+        try:
+            for pass_, want in zip(L.CONV_PASSES, passes):
+                if want is None:
+                    continue
+                family, fig = want
+                flags = dict(kw)
+                if pass_ == "wgrad":
+                    flags.setdefault("ws", True)
+                assert ops.conv_path(g, dtype, pass_, **flags) == family, (case, kw, opts, pass_)
+                p = g.params(dtype)
+                p.splitk = flags.get("splitk", 0)
+                if pass_ == "wgrad":
+                    ktot = g.kh * g.kw * g.cin
+                    ws = {"wpatch": 128 * 64 * 576, "stem_wpatch": 256 * 64 * 392}.get(family)
+                    if ws is None and fig is not None:
+                        ws = g.groups * fig * g.cout * ktot if fig > 1 else 0
+                    if ws is not None:
+                        assert lib.avsr_conv_wgrad_ws(ctypes.byref(p)) == ws, (case, kw, opts)
+                elif family == "s2":
+                    cls = [g.nimg * ((g.hin - a + 1) // 2) * ((g.win - b + 1) // 2) for a in (0, 1) for b in (0, 1)]
+                    assert lib.avsr_conv_bnr_tiles(ctypes.byref(p)) == sum(-(-m // fig) for m in cls), (case, kw, opts)
+                elif pass_ == "fwd":
+                    assert lib.avsr_conv_stat_tiles(ctypes.byref(p)) == -(-g.out_pixels // fig), (case, kw, opts)
+                else:
+                    assert lib.avsr_conv_bnr_tiles(ctypes.byref(p)) == -(-g.in_pixels // fig), (case, kw, opts)
+        finally:
+            for k, v in prev.items():
+                L.set_option(k, v)
+    assert all(L.get_option(k) == 1 for k in ("conv_192", "conv_s2phase", "conv_patch", "conv_wpatch", "stem_wpatch"))
+    for pass_ in L.CONV_PASSES:
+        with pytest.raises(L.AvsrLibError, match="1001"):                   # AVSR_E_SHAPE: cin no power of two
+            ops.conv_path(_conv_geom((6, 22, 22, 48, 64, 3, 1, 1)), L.AVSR_BF16, pass_)
+        with pytest.raises(L.AvsrLibError, match="1002"):                   # AVSR_E_ALIGN: ldx % 8
+            ops.conv_path(_conv_geom(_S1, ldx=68), L.AVSR_BF16, pass_)
+        with pytest.raises(L.AvsrLibError, match="1003"):                   # AVSR_E_DTYPE
+            ops.conv_path(_conv_geom(_S1), 7, pass_)
+    p = _conv_geom(_S1).params(L.AVSR_BF16)
+    assert lib.avsr_conv_path(ctypes.byref(p), 3) == 1004                    # AVSR_E_ARG: no such pass
+    assert lib.avsr_conv_path(ctypes.byref(p), -1) == 1004
+    assert lib.avsr_conv_path(None, 0) == 1004
+
+
 def _header_option_defaults():
     """{AVSR_OPT_name: default} from the bracketed defaults in avsr_hip.h's option table"""
     src = open(os.path.join(ROOT, "include", "avsr_hip.h")).read()

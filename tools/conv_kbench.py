@@ -1,6 +1,6 @@
 """Isolated ResNet-frontend kernels at C2 (6000 images), HIP-event timed, median of reps:
 stem conv (general path: pack + 7x7 implicit GEMM, vs stem.hip straight from the video) and
-the stage-1 3x3 convolutions (forward, fused BN-backward data-grad, weight-grad) with the
+the stage-1 3x3 convolutions (forward, plain and fused BN-backward data-grad, weight-grad) with the
 patch-resident kernel on / off. usage: python tools/conv_kbench.py [reps]"""
 import json
 import os
@@ -74,6 +74,7 @@ p1 = torch.empty(64, ops.conv_stat_tiles(geom, ops.dtype_code(x)), 3, device=dev
 for flag in ("0", "1"):
     L.set_option("conv_patch", int(flag))
     res[f"s1_fwd_patch{flag}"] = timed(lambda: ops.conv_fwd(geom, x, w, y, p1))
+    res[f"s1_dgrad_patch{flag}"] = timed(lambda: ops.conv_bwd_data(geom, dy, w, dx))
     res[f"s1_dgrad_bnr_patch{flag}"] = timed(lambda: ops.conv_bwd_data_bnr(geom, dy, w, dx, hh, st, a, beta=0.0))
     res[f"s1_dgrad_bnr_id_patch{flag}"] = timed(lambda: ops.conv_bwd_data_bnr(geom, dy, w, dx, hh, st, a, res=x,
                                                                              beta=1.0))

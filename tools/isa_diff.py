@@ -1,8 +1,9 @@
 """Compare the kernels of device assembly files (hipcc --cuda-device-only -S) after a source move:
 python tools/isa_diff.py parent.s new_a.s [new_b.s ...]. Kernels are matched by demangled name with
-the namespaces given by --ns (default: the anonymous one, attn, f32) dropped, and a parent's
+the namespaces given by --ns (default: the anonymous one, attn, f32, conv) dropped, and a parent's
 K<float>(..) with a new plain K(..); a body is its text from the label to .Lfunc_end with comments stripped, local
-labels renumbered and other symbols' names blanked; the resources are its .amdhsa_ lines."""
+labels renumbered and other symbols' names blanked; the resources are its .amdhsa_ lines. A kernel that
+several new files hold (a static __global__ of a shared header) is compared once per copy."""
 import argparse
 import re
 import subprocess
@@ -44,7 +45,7 @@ def load(paths, ns):
             key = re.sub(r"^void ", "", pretty)
             for n in ns:
                 key = key.replace(n + "::", "")
-            out[key] = (body(ks[name]), res[name], p)
+            out.setdefault(key, []).append((body(ks[name]), res[name], p))
     return out
 
 
@@ -60,17 +61,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("parent")
     ap.add_argument("new", nargs="+")
-    ap.add_argument("--ns", default="(anonymous namespace),attn,f32")
+    ap.add_argument("--ns", default="(anonymous namespace),attn,f32,conv")
     a = ap.parse_args()
     ns = a.ns.split(",")
     old, new = load([a.parent], ns), load(a.new, ns)
     untemplated(old, new)
-    same = 0
-    for key in sorted(set(old) | set(new)):
-        if key not in old or key not in new:
-            print("ONLY IN", "parent" if key in old else new[key][2], key)
+    same = copies = 0
+    none = [(None, None, None)]
+    for key, (b1, r1, path) in sorted(((k, c) for k in set(old) | set(new) for c in new.get(k, none)), key=lambda kc: kc[0]):
+        if key not in old or b1 is None:
+            print("ONLY IN", "parent" if key in old else path, key)
             continue
-        (b0, r0, _), (b1, r1, path) = old[key], new[key]
+        b0, r0, _ = old[key][0]
+        copies += 1
         rdiff = {k: (r0.get(k), r1.get(k)) for k in set(r0) | set(r1) if r0.get(k) != r1.get(k)}
         r = r1
         tag = "identical" if b0 == b1 and not rdiff else "DIFFERS"
@@ -82,7 +85,8 @@ def main():
                   f"{next((i for i, (x, y) in enumerate(zip(b0, b1)) if x != y), min(len(b0), len(b1)))}")
         for k, v in sorted(rdiff.items()):
             print(f"    {k}: {v[0]} -> {v[1]}")
-    print(f"kernels: parent {len(old)}, new {len(new)}, compared {len(set(old) & set(new))}, identical {same}")
+    print(f"kernels: parent {len(old)}, new {len(new)} in {sum(map(len, new.values()))} copies, compared {copies}, "
+          f"identical {same}")
 
 
 if __name__ == "__main__":
