@@ -43,7 +43,7 @@ class GemmParams(ctypes.Structure):
         ("stamp", _c_p),
         ("skinny_ws", _c_p), ("ln_c1", _c_p), ("ln_eps", ctypes.c_float),
         ("kv_k", _c_p), ("kv_v", _c_p), ("kv_pos", _c_p), ("kv_rows", _i),
-        ("slab_cnt", _c_p),
+        ("slab_cnt", _c_p), ("kv_pos_stride", _i),
     ]
 
 
@@ -165,7 +165,7 @@ class EmbedParams(ctypes.Structure):
     _fields_ = [
         ("dtype", _i), ("rows", _i), ("L", _i), ("D", _i), ("tok", _c_p), ("table", _c_p), ("pe", _c_p),
         ("scale", _f), ("y", _c_p), ("drop_p", _f), ("seed", ctypes.c_uint64), ("dy", _c_p), ("dtable", _c_p),
-        ("pe_row", _c_p),
+        ("pe_row", _c_p), ("pe_row_stride", _i),
     ]
 
 
@@ -213,6 +213,7 @@ class CtcPrefixParams(ctypes.Structure):
         ("n", _i), ("T", _i), ("V", _i), ("P", _i), ("blank", _i), ("eos", _i), ("out_len", _i),
         ("logp", _c_p), ("r_prev", _c_p), ("last", _c_p), ("ids", _c_p), ("r_new", _c_p), ("psi", _c_p),
         ("uidx", _c_p), ("logp_ustride", _i64), ("tlen", _c_p), ("out_len_dev", _c_p),
+        ("out_len_stride", _i),
     ]
 
 
@@ -234,6 +235,16 @@ class BeamPostParams(ctypes.Structure):
         ("tok", _c_p), ("score", _c_p), ("sdec", _c_p), ("sctc", _c_p), ("s_prev", _c_p), ("src", _c_p),
         ("bp_prev", _c_p), ("bp_tok", _c_p), ("end_flag", _c_p), ("end_score", _c_p), ("end_dec", _c_p),
         ("end_ctc", _c_p), ("best_len", _c_p), ("best_end", _c_p), ("done", _c_p),
+        ("upos", _c_p), ("rowpos", _c_p),
+    ]
+
+
+class BeamSlotResetParams(ctypes.Structure):
+    _fields_ = [
+        ("U", _i), ("beam", _i), ("R", _i), ("Lmax", _i), ("slot", _i), ("sos", _i), ("maxlen", _i), ("tlen", _i),
+        ("upos", _c_p), ("rowpos", _c_p), ("done", _c_p),
+        ("tok", _c_p), ("score", _c_p), ("sdec", _c_p), ("sctc", _c_p), ("s_prev", _c_p),
+        ("best_len", _c_p), ("best_end", _c_p), ("maxlen_arr", _c_p), ("tlen_arr", _c_p), ("klen_mem", _c_p),
     ]
 
 
@@ -330,6 +341,9 @@ SYMBOLS = {
     "avsr_beam_step_prep": ([_i, _i, _c_p, _c_p, _c_p, _c_p], _i),
     "avsr_beam_kv_put": ([_i, _i, _i, _c_p, _i64, _c_p, _c_p, _c_p, _c_p], _i),
     "avsr_beam_post": ([ctypes.POINTER(BeamPostParams), _c_p], _i),
+    "avsr_beam_step_prep_rows": ([_i, _i, _c_p, _c_p, _c_p, _c_p], _i),
+    "avsr_beam_kv_put_rows": ([_i, _i, _i, _c_p, _i64, _c_p, _c_p, _c_p, _c_p], _i),
+    "avsr_beam_slot_reset": ([ctypes.POINTER(BeamSlotResetParams), _c_p], _i),
     "avsr_gather_rows": ([_i, _i, _i64, _c_p, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p], _i),
     "avsr_fbank_stack": ([ctypes.POINTER(FbankParams), _c_p], _i),
     "avsr_video_normalize": ([ctypes.POINTER(VideoNormParams), _c_p], _i),

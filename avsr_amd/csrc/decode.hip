@@ -408,7 +408,7 @@ __global__ __launch_bounds__(256) void log_softmax_topk_kernel(int V, int K, con
 // hypothesis, lane j = its j-th scored token; the T recursion is sequential per lane.
 __global__ __launch_bounds__(64) void ctc_prefix_kernel(avsr_ctc_prefix_params p) {
   const int h = blockIdx.x, j = threadIdx.x;
-  if (p.out_len_dev) p.out_len = p.out_len_dev[0];
+  if (p.out_len_dev) p.out_len = p.out_len_dev[h * p.out_len_stride];
   const int V = p.V;
   const int u = p.uidx ? p.uidx[h] : 0;
   const int T = p.uidx ? p.tlen[u] : p.T;         // this utterance's frames
@@ -417,11 +417,13 @@ __global__ __launch_bounds__(64) void ctc_prefix_kernel(avsr_ctc_prefix_params p
   const bool act = j < p.P;
   const int id = act ? p.ids[h * p.P + j] : 0;
   const bool same = act && id == p.last[h];
-  const float* rp = p.r_prev ? p.r_prev + (int64_t)h * TS * 2 : nullptr;
+  // (per-row lengths: a row of length 0 is at its first step whatever the launch's r_prev holds)
+  const bool first = !p.r_prev || (p.out_len_stride && p.out_len == 0);
+  const float* rp = first ? nullptr : p.r_prev + (int64_t)h * TS * 2;
   float* rn = act ? p.r_new + ((int64_t)h * p.P + j) * TS * 2 : nullptr;
   // r_prev at the first step: (logzero, cumsum of blank log-probs)
   auto rprev = [&](int t, int q, float cum) -> float { return rp ? rp[t * 2 + q] : (q == 0 ? LOGZERO : cum); };
-  const int start = max(p.out_len, 1);
+  const int start = min(max(p.out_len, 1), T);     // (a dead row past its frames stays inside them)
   // values of r for t < start
   float r0 = LOGZERO, r1 = LOGZERO;
   float cum = 0.f;          // running cumsum of logp[t][blank] (first step only)
@@ -478,7 +480,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_lds_kernel(avsr_ctc_prefix_par
   extern __shared__ float sm[];
   __shared__ int sid[65];
   const int h = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int out_len = p.out_len_dev ? p.out_len_dev[0] : p.out_len;
+  const int out_len = p.out_len_dev ? p.out_len_dev[h * p.out_len_stride] : p.out_len;
   const int V = p.V, P = p.P, W = P + 1;
   const int u = p.uidx ? p.uidx[h] : 0;
   const int T = p.uidx ? p.tlen[u] : p.T;
@@ -489,7 +491,9 @@ __global__ __launch_bounds__(256) void ctc_prefix_lds_kernel(avsr_ctc_prefix_par
   const int* __restrict__ ids = p.ids + h * P;
   if (tid < P) sid[tid] = ids[tid];
   if (tid == P) sid[P] = p.blank;
-  const float* __restrict__ rp = p.r_prev ? p.r_prev + (int64_t)h * TS * 2 : nullptr;
+  // (per-row lengths: a row of length 0 is at its first step whatever the launch's r_prev holds)
+  const bool first = !p.r_prev || (p.out_len_stride && out_len == 0);
+  const float* __restrict__ rp = first ? nullptr : p.r_prev + (int64_t)h * TS * 2;
   if (rp)
     for (int t = tid; t < T; t += 256) {
       const float a0 = rp[2 * t], a1 = rp[2 * t + 1];
@@ -746,9 +750,11 @@ extern "C" int avsr_log_softmax_topk(int dtype, int rows, int V, const void* x, 
 }
 
 // ---------------------------------------------------------------- device-side bookkeeping
-__global__ __launch_bounds__(256) void beam_step_prep_kernel(int R, int Lmax, const int* pos_p, int* anc, int* klen) {
-  const int pos = pos_p[0];
+// ps = 0: one shared position pos_p[0]; ps = 1: one per row (a decode session's rowpos)
+__global__ __launch_bounds__(256) void beam_step_prep_kernel(int R, int Lmax, const int* pos_p, int ps, int* anc,
+                                                             int* klen) {
   for (int r = blockIdx.x * 256 + threadIdx.x; r < R; r += gridDim.x * 256) {
+    const int pos = pos_p[r * ps];
     anc[(int64_t)r * Lmax + pos] = pos * R + r;
     klen[r] = pos + 1;
   }
@@ -756,29 +762,32 @@ __global__ __launch_bounds__(256) void beam_step_prep_kernel(int R, int Lmax, co
 
 template <typename T>
 __global__ __launch_bounds__(256) void beam_kv_put_kernel(int R, int D, const T* qkv, int64_t ld, T* ck, T* cv,
-                                                          const int* pos_p) {
-  const int pos = pos_p[0];
+                                                          const int* pos_p, int ps) {
   const int nv = D / VecW<T>::VE;
   for (int e = blockIdx.x * 256 + threadIdx.x; e < R * nv; e += gridDim.x * 256) {
     const int r = e / nv, c = (e - r * nv) * VecW<T>::VE;
+    const int pos = pos_p[r * ps];
     const int64_t dst = ((int64_t)pos * R + r) * D + c;
     *(v16*)(ck + dst) = *(const v16*)(qkv + (int64_t)r * ld + D + c);
     *(v16*)(cv + dst) = *(const v16*)(qkv + (int64_t)r * ld + 2 * D + c);
   }
 }
 
-// one workgroup: rows of the step (R <= 1024), then one thread per utterance
+// one workgroup: rows of the step (R <= 1024), then one thread per utterance. With p.upos the
+// position is per utterance slot (upos[u]); a slot done before the step keeps it, every other
+// advances, and rowpos[r] = upos[r / beam] is rewritten.
 __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   double* od = (double*)sm;                   // [R] old decoder sums
   double* oc = od + p.R;                      // [R] old CTC sums
   int* ended = (int*)(oc + p.R);              // [R] 0 running, 1 eos, 2 forced eos at maxlen
-  const int pos = p.pos[0];
+  const int pos0 = p.upos ? 0 : p.pos[0];
   for (int r = threadIdx.x; r < p.R; r += 256) { od[r] = p.sdec[r]; oc[r] = p.sctc[r]; }
   __syncthreads();
-  const int64_t so = (int64_t)pos * p.R;
   for (int r = threadIdx.x; r < p.R; r += 256) {
     const int u = r / p.beam;
+    const int pos = p.upos ? p.upos[u] : pos0;
+    const int64_t so = (int64_t)pos * p.R;
     ended[r] = 0;
     if (p.done[u]) {                          // finished before this step: stays dead
       p.score[r] = -INFINITY;
@@ -803,6 +812,8 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
   const int LB = p.Lmax + 3;
   for (int u = threadIdx.x; u < p.U; u += 256) {
     if (p.done[u]) continue;
+    const int pos = p.upos ? p.upos[u] : pos0;
+    const int64_t so = (int64_t)pos * p.R;
     bool any_live = false;
     float* bl = p.best_len + (int64_t)u * LB;
     for (int k = 0; k < p.beam; ++k) {         // this step's ended hypotheses, in selection order
@@ -826,43 +837,94 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
       p.done[u] = 1;
       for (int k = 0; k < p.beam; ++k) p.score[u * p.beam + k] = -INFINITY;
     }
+    if (p.upos) p.upos[u] = pos + 1;
   }
   __syncthreads();
+  if (p.upos)
+    for (int r = threadIdx.x; r < p.R; r += 256) p.rowpos[r] = p.upos[r / p.beam];
   if (threadIdx.x == 0) {
     int n = 0;
     for (int u = 0; u < p.U; ++u) n += p.done[u];
     p.done[p.U] = n;
-    p.pos[0] = pos + 1;
+    if (!p.upos) p.pos[0] = pos0 + 1;
   }
 }
 
-extern "C" int avsr_beam_step_prep(int R, int Lmax, const int* pos, int* anc, int* klen, void* stream) {
+// slot p.slot of a decode session back to the state of a fresh utterance (only its rows)
+__global__ __launch_bounds__(256) void beam_slot_reset_kernel(avsr_beam_slot_reset_params p) {
+  const int u = p.slot, r0 = u * p.beam;
+  for (int k = threadIdx.x; k < p.beam; k += 256) {
+    const int r = r0 + k;
+    p.rowpos[r] = 0;
+    p.tok[r] = p.sos;
+    p.score[r] = k == 0 ? 0.f : -INFINITY;
+    p.sdec[r] = 0.0; p.sctc[r] = 0.0; p.s_prev[r] = 0.f;
+    p.klen_mem[r] = p.tlen;
+  }
+  float* bl = p.best_len + (int64_t)u * (p.Lmax + 3);
+  for (int k = threadIdx.x; k < p.Lmax + 3; k += 256) bl[k] = -INFINITY;
+  if (threadIdx.x == 0) {
+    p.upos[u] = 0;
+    p.best_end[u] = -INFINITY;
+    p.maxlen_arr[u] = p.maxlen;
+    p.tlen_arr[u] = p.tlen;
+    int n = 0;
+    for (int v = 0; v < p.U; ++v) n += v == u ? 0 : p.done[v];
+    p.done[u] = 0;
+    p.done[p.U] = n;
+  }
+}
+
+static int beam_step_prep(int R, int Lmax, const int* pos, int ps, int* anc, int* klen, void* stream) {
   if (R <= 0 || Lmax <= 0 || !pos || !anc || !klen) return AVSR_E_ARG;
-  hipLaunchKernelGGL(beam_step_prep_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, R, Lmax, pos, anc,
-                     klen);
+  hipLaunchKernelGGL(beam_step_prep_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, R, Lmax, pos, ps,
+                     anc, klen);
   AVSR_CHECK_LAUNCH();
   return 0;
 }
+extern "C" int avsr_beam_step_prep(int R, int Lmax, const int* pos, int* anc, int* klen, void* stream) {
+  return beam_step_prep(R, Lmax, pos, 0, anc, klen, stream);
+}
+extern "C" int avsr_beam_step_prep_rows(int R, int Lmax, const int* rowpos, int* anc, int* klen, void* stream) {
+  return beam_step_prep(R, Lmax, rowpos, 1, anc, klen, stream);
+}
 
-extern "C" int avsr_beam_kv_put(int dtype, int R, int D, const void* qkv, int64_t ldqkv, void* cache_k, void* cache_v,
-                                const int* pos, void* stream) {
+static int beam_kv_put(int dtype, int R, int D, const void* qkv, int64_t ldqkv, void* cache_k, void* cache_v,
+                       const int* pos, int ps, void* stream) {
   const int ve = dtype == AVSR_BF16 ? 8 : 4;
   if (R <= 0 || D % ve || ldqkv % ve || !pos) return AVSR_E_ARG;
   if (!avsr_aligned16(qkv) || !avsr_aligned16(cache_k) || !avsr_aligned16(cache_v)) return AVSR_E_ALIGN;
   const int g = avsr_grid((int64_t)R * D / ve, 256, 1024);
   if (dtype == AVSR_BF16)
     hipLaunchKernelGGL(beam_kv_put_kernel<bf16>, dim3(g), dim3(256), 0, (hipStream_t)stream, R, D, (const bf16*)qkv, ldqkv,
-                       (bf16*)cache_k, (bf16*)cache_v, pos);
+                       (bf16*)cache_k, (bf16*)cache_v, pos, ps);
   else if (dtype == AVSR_F32)
     hipLaunchKernelGGL(beam_kv_put_kernel<float>, dim3(g), dim3(256), 0, (hipStream_t)stream, R, D, (const float*)qkv,
-                       ldqkv, (float*)cache_k, (float*)cache_v, pos);
+                       ldqkv, (float*)cache_k, (float*)cache_v, pos, ps);
   else return AVSR_E_DTYPE;
+  AVSR_CHECK_LAUNCH();
+  return 0;
+}
+extern "C" int avsr_beam_kv_put(int dtype, int R, int D, const void* qkv, int64_t ldqkv, void* cache_k, void* cache_v,
+                                const int* pos, void* stream) {
+  return beam_kv_put(dtype, R, D, qkv, ldqkv, cache_k, cache_v, pos, 0, stream);
+}
+extern "C" int avsr_beam_kv_put_rows(int dtype, int R, int D, const void* qkv, int64_t ldqkv, void* cache_k,
+                                     void* cache_v, const int* rowpos, void* stream) {
+  return beam_kv_put(dtype, R, D, qkv, ldqkv, cache_k, cache_v, rowpos, 1, stream);
+}
+
+extern "C" int avsr_beam_slot_reset(const avsr_beam_slot_reset_params* p, void* stream) {
+  if (!p || p->U <= 0 || p->beam <= 0 || p->R != p->U * p->beam || p->slot < 0 || p->slot >= p->U) return AVSR_E_ARG;
+  if (p->maxlen < 1 || p->maxlen >= p->Lmax || p->tlen < 1) return AVSR_E_SHAPE;
+  hipLaunchKernelGGL(beam_slot_reset_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *p);
   AVSR_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int avsr_beam_post(const avsr_beam_post_params* p, void* stream) {
   if (!p || p->U <= 0 || p->beam <= 0 || p->R != p->U * p->beam || p->R > 2048) return AVSR_E_ARG;
+  if (p->upos ? !p->rowpos : !p->pos) return AVSR_E_ARG;
   const size_t lds = (size_t)p->R * (2 * sizeof(double) + sizeof(int));
   hipLaunchKernelGGL(beam_post_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, *p);
   AVSR_CHECK_LAUNCH();
@@ -906,6 +968,7 @@ extern "C" int avsr_row_topk(const avsr_topk_params* p, void* stream) {
 extern "C" int avsr_ctc_prefix(const avsr_ctc_prefix_params* p, void* stream) {
   if (!p || p->n <= 0) return AVSR_E_ARG;
   if (p->P < 1 || p->P > 64 || p->T < 1) return AVSR_E_SHAPE;
+  if (p->out_len_stride && !p->out_len_dev) return AVSR_E_ARG;
   const size_t lds = (size_t)p->T * (p->P + 1 + 2) * sizeof(float);
   if (lds <= 64 * 1024)
     hipLaunchKernelGGL(ctc_prefix_lds_kernel, dim3(p->n), dim3(256), lds, (hipStream_t)stream, *p);

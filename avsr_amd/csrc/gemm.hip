@@ -323,7 +323,7 @@ int check_params(const avsr_gemm_params* p, int splits, bool slab, bool glds) {
     return AVSR_E_ARG;
   const bool skinny = !glds && !slab && skinny_ok(p, splits);
   if (p->kv_k && (p->dtype != AVSR_F32 || p->M > 64 || splits > 1 || (p->N % 3) || !p->kv_v || !p->kv_pos ||
-                  p->kv_rows < p->M))
+                  p->kv_rows < p->M || p->kv_pos_stride < 0))
     return AVSR_E_ARG;
   if (p->kv_k && !skinny) return AVSR_E_ARG;
   if (p->ln_c1 && (p->dtype != AVSR_F32 || p->M > 64 || splits > 1)) return AVSR_E_ARG;
@@ -367,7 +367,7 @@ DenseArgs gemmd::dense_args(const avsr_gemm_params* p, int splits, bool slab) {
   a.stamp = p->stamp;
   a.falpha = 1.f;
   a.ln_c1 = p->ln_c1; a.ln_eps = p->ln_eps;
-  a.kvk = (float*)p->kv_k; a.kvv = (float*)p->kv_v; a.kvpos = p->kv_pos; a.kvrows = p->kv_rows;
+  a.kvk = (float*)p->kv_k; a.kvv = (float*)p->kv_v; a.kvpos = p->kv_pos; a.kvrows = p->kv_rows; a.kvposs = p->kv_pos_stride;
   Epi& e = a.e;   // (the fields the conv epilogues use stay zero)
   e.M = p->M; e.N = p->N; e.C = p->C; e.ldc = p->ldc;
   e.alpha = p->alpha; e.beta = p->beta; e.bias = p->bias;

@@ -21,7 +21,7 @@ struct DenseArgs {
   float falpha, fbeta;
   const float* ln_c1; float ln_eps;   // skinny_mma_kernel LayerNorm prologue (avsr_gemm_params.ln_c1)
   float* lnst;                        // ... its per-chunk row statistics (split launches)
-  float* kvk; float* kvv; const int* kvpos; int kvrows;   // KV-cache append (avsr_gemm_params.kv_k)
+  float* kvk; float* kvv; const int* kvpos; int kvrows; int kvposs;   // KV-cache append (avsr_gemm_params.kv_k)
 };
 
 // the epilogue arguments of one output tile's batch / K split, pinned to the variant EV

@@ -282,7 +282,7 @@ __global__ __launch_bounds__(64 * SKM_WAVES) void skinny_mma_kernel(DenseArgs a,
       y = act_fwd_t<float>(e.act, y);
       if (e.res) y += pr[i];
       if (a.kvk && cl >= kvD) {  // K / V columns: appended to the cache at this step's rows
-        const int64_t row = (int64_t)(*a.kvpos) * a.kvrows + m;
+        const int64_t row = (int64_t)a.kvpos[m * a.kvposs] * a.kvrows + m;
         float* dst = cl < 2 * kvD ? a.kvk : a.kvv;
         dst[row * kvD + (cl < 2 * kvD ? cl - kvD : cl - 2 * kvD)] = y;
       } else {

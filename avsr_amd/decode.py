@@ -15,6 +15,11 @@ top-beam, running scores, back-pointers, ended-hypothesis records, end detection
 step after the first is one HIP-graph replay; the host reads a finished-utterance count every
 8 steps and the history once at the end — the reference synchronises per hypothesis.
 
+A stream of utterances of unequal length goes through a `DecodeSession` (`bs.stream()`,
+`bs.decode_stream(xs)`): a fixed number of utterance slots whose graphs are captured once, a
+finished utterance's slot refilled with the next input while the others keep stepping
+(continuous batching). There the position is kept per row, not once for the batch.
+
 Differences that do not change results: the cross-attention K/V of the memory are computed
 once per utterance (the reference recomputes them every step), the self-attention K/V of
 earlier positions are cached instead of the layer outputs they are computed from (rows of
@@ -36,6 +41,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import stream_slots
 
 LOGZERO = -10000000000.0
 # fp32 decode: LayerNorms folded into the linears they feed (the few-row kernel's LN prologue)
@@ -130,8 +136,9 @@ class BatchBeamSearch:
         ar = eng.arena
         D, H, R = eng.dD, eng.dH, st["R"]
         pos, cache, anc = st["pos"], st["cache"], st["anc_in"]
+        pr = "rowpos" in st                     # a session's state: pos holds one position per row
         x = eng._e(R, D)
-        ops.embed_fwd(st["tok"], eng.w("decoder.embed.0.weight"), eng._pe, math.sqrt(D), x, 1, pe_row=pos)
+        ops.embed_fwd(st["tok"], eng.w("decoder.embed.0.weight"), eng._pe, math.sqrt(D), x, 1, pe_row=pos, per_row=pr)
         Tm = st["Tm"]
         fold = st.get("fold")
         for i in range(eng.dl):
@@ -140,13 +147,13 @@ class BatchBeamSearch:
             kc, vc = cache[i, 0], cache[i, 1]               # (Lmax * R, D): rows step * R + r
             if fold is not None:       # norm1 folded into the QKV linear, K / V appended to the cache (one launch)
                 Wg, bb, c1 = fold[i]["qkv"]
-                qkv = ops.linear_fwd(x, Wg, bb, ln=(c1, 1e-12), kv=(kc, vc, pos, R))
+                qkv = ops.linear_fwd(x, Wg, bb, ln=(c1, 1e-12), kv=(kc, vc, pos, R, pr))
             else:
                 n1, _, _ = ops.layernorm_fwd(x, ar.master(p + "norm1.weight"), ar.master(p + "norm1.bias"), 1e-12)
                 qkv = ops.linear_fwd(n1, ar.span([sa + "linear_q.weight", sa + "linear_k.weight", sa + "linear_v.weight"]),
                                      ar.span([sa + "linear_q.bias", sa + "linear_k.bias", sa + "linear_v.bias"],
                                              buf="master"))
-                ops.beam_kv_put(qkv, kc, vc, pos, R, D)
+                ops.beam_kv_put(qkv, kc, vc, pos, R, D, per_row=pr)
             o1 = eng._e(R, D)
             ops.dec_attn(qkv[:, :D], kc, vc, o1, n=R, H=H, klen_max=st["Lmax"], k_bstride=0, v_bstride=0,
                          klen=st["klen_self"], kmap=anc)
@@ -207,7 +214,8 @@ class BatchBeamSearch:
         the row's top-P tokens by psi into st["ids"] (the kernel's psi of a token does not depend
         on the other ids of its launch)"""
         R, V = st["R"], self.n_vocab
-        kw = dict(n=R, out_len=0, out_len_dev=st["pos"], blank=self.blank, eos=self.eos, uidx=st["uidx"], tlen=st["tlen"])
+        kw = dict(n=R, out_len=0, out_len_dev=st["pos"], per_row="rowpos" in st, blank=self.blank, eos=self.eos,
+                  uidx=st["uidx"], tlen=st["tlen"])
         pf = st["psi_full"]
         for c in range(st["vchunks"].shape[0]):
             ops.ctc_prefix(st["logp"], r_prev, st["tok"], st["vchunks"][c], st["r_scr"], st["psi_c"], **kw)
@@ -220,7 +228,7 @@ class BatchBeamSearch:
         and CTC-state ping-pong buffers (read k, write 1 - k)."""
         R, P, beam = st["R"], self.pre_beam_size, self.beam_size
         st["anc_in"] = st["anc"][k]
-        ops.beam_step_prep(R, st["pos"], st["anc"][k], st["klen_self"])
+        ops.beam_step_prep(R, st["pos"], st["anc"][k], st["klen_self"], per_row="rowpos" in st)
         # decoder log-probs + the pre-beam ids; without a decoder scorer its score is 0
         dec = self._decoder_step(eng, st) if self.use_dec else st["dec0"]
         if self.use_ctc:
@@ -228,7 +236,8 @@ class BatchBeamSearch:
             if not self.use_dec:
                 self._ctc_full_vocab(st, r_prev)
             ops.ctc_prefix(st["logp"], r_prev, st["tok"], st["ids"], st["r_new"], st["psi"], n=R, out_len=0,
-                           out_len_dev=st["pos"], blank=self.blank, eos=self.eos, uidx=st["uidx"], tlen=st["tlen"])
+                           out_len_dev=st["pos"], per_row="rowpos" in st, blank=self.blank, eos=self.eos,
+                           uidx=st["uidx"], tlen=st["tlen"])
         out = st["out"]
         ops.beam_select(dec, self.n_vocab, st["ids"], st["psi"], st["s_prev"], st["score"], out, n=R, beam=beam,
                         blank=self.blank, eos=self.eos, w_dec=self.w_dec, w_ctc=self.w_ctc, seg=st["seg"])
@@ -238,7 +247,8 @@ class BatchBeamSearch:
                       sel_dec=out["dec"], sel_ctc=out["ctc"], sel_s=out["s"], tok=st["tok"], score=st["score"],
                       sdec=st["sdec"], sctc=st["sctc"], s_prev=st["s_prev"], src=st["src"], bp_prev=st["bp_prev"],
                       bp_tok=st["bp_tok"], end_flag=st["end_flag"], end_score=st["end_score"], end_dec=st["end_dec"],
-                      end_ctc=st["end_ctc"], best_len=st["best_len"], best_end=st["best_end"], done=st["done"])
+                      end_ctc=st["end_ctc"], best_len=st["best_len"], best_end=st["best_end"], done=st["done"],
+                      upos=st.get("upos"), rowpos=st.get("rowpos"))
         Lm, Tm = st["Lmax"], st["Tm"]
         ops.gather_rows(st["anc"][k], st["anc"][1 - k], st["src"][:R], groups=1, n=R, row_bytes=Lm * 4,
                         src_gstride=0, src_rstride=Lm * 4, dst_gstride=0, dst_rstride=Lm * 4)
@@ -378,28 +388,35 @@ class BatchBeamSearch:
         torch.cuda.current_stream(dev).wait_stream(s)
         return graphs
 
+    def _ended_hyps(self, st, n, r0, rows):
+        """the ended hypotheses recorded in history columns [r0, r0 + rows) over the first n steps,
+        as [(column - r0, Hypothesis)] in the reference's order (step, then selection rank), yseq
+        rebuilt from the back-pointers (global row indices, all inside the column range: the
+        rows of the utterances it holds)"""
+        col = slice(r0, r0 + rows)
+        bp_prev, bp_tok, flag, esc, edec, ectc = (st[k][:n, col].cpu().numpy() for k in
+                                                  ("bp_prev", "bp_tok", "end_flag", "end_score", "end_dec", "end_ctc"))
+        out = []
+        for i in range(n):
+            for r in np.nonzero(flag[i])[0].tolist():
+                toks = [int(bp_tok[i, r])]
+                h = int(bp_prev[i, r]) - r0
+                for j in range(i - 1, -1, -1):
+                    toks.append(int(bp_tok[j, h]))
+                    h = int(bp_prev[j, h]) - r0
+                yseq = [self.sos] + toks[::-1] + ([self.eos] if flag[i, r] == 2 else [])
+                out.append((r, self._make_hyp(dict(yseq=yseq, score=float(esc[i, r]), dec=float(edec[i, r]),
+                                                   ctc=float(ectc[i, r])), self.use_dec, self.use_ctc)))
+        return out
+
     def _collect(self, st, xs, maxlenratio, minlenratio):
         """ended hypotheses from the device history, per utterance in the reference's order
         (step, then selection rank), yseq rebuilt from the back-pointers"""
         U, R, beam = st["U"], st["R"], self.beam_size
         n = min(int(st["pos"].item()), st["steps"])
-        bp_prev = st["bp_prev"][:n].cpu().numpy()
-        bp_tok = st["bp_tok"][:n].cpu().numpy()
-        flag = st["end_flag"][:n].cpu().numpy()
-        esc = st["end_score"][:n].cpu().numpy()
-        edec = st["end_dec"][:n].cpu().numpy()
-        ectc = st["end_ctc"][:n].cpu().numpy()
         ended = [[] for _ in range(U)]
-        for i in range(n):
-            for r in np.nonzero(flag[i])[0].tolist():
-                toks = [int(bp_tok[i, r])]
-                h = int(bp_prev[i, r])
-                for j in range(i - 1, -1, -1):
-                    toks.append(int(bp_tok[j, h]))
-                    h = int(bp_prev[j, h])
-                yseq = [self.sos] + toks[::-1] + ([self.eos] if flag[i, r] == 2 else [])
-                ended[r // beam].append(self._make_hyp(dict(yseq=yseq, score=float(esc[i, r]), dec=float(edec[i, r]),
-                                                            ctc=float(ectc[i, r])), self.use_dec, self.use_ctc))
+        for r, hyp in self._ended_hyps(st, n, 0, R):
+            ended[r // beam].append(hyp)
         results = []
         for u in range(U):
             nbest = sorted(ended[u], key=lambda h: float(h.score), reverse=True)
@@ -407,6 +424,91 @@ class BatchBeamSearch:
                 nbest = self.forward(xs[u], maxlenratio, max(0.0, minlenratio - 0.1))
             results.append(nbest)
         return results
+
+    # ----------------------------------------------------------------------- streaming
+    def stream(self, slots=None, max_frames=375, maxlenratio=0.0, minlenratio=0.0, poll=4, graphs=True):
+        """A persistent decode session of `slots` utterance slots x beam rows (see DecodeSession);
+        slots=None: min(8, 64 // beam)."""
+        return DecodeSession(self, slots, max_frames, maxlenratio, minlenratio, poll, graphs)
+
+    def decode_stream(self, xs, **kw):
+        """The n-best lists of the encoded utterances xs in input order, decoded through a session
+        (`stream(**kw)`) that refills a slot as soon as its utterance ends. Per utterance the result
+        is that of `self(x)`."""
+        xs = list(xs)
+        with self.stream(**kw) as session:
+            return stream_slots.in_input_order(session.run(xs), len(xs))
+
+    @staticmethod
+    def _maxlen(T, maxlenratio):
+        """steps of an utterance of T frames (decode_batch's rule)"""
+        return T if maxlenratio == 0 else (-int(maxlenratio) if maxlenratio < 0 else max(1, int(maxlenratio * T)))
+
+    def _session_buffers(self, S, max_frames):
+        """what a session owns besides the search state: (engine, device, dtype, D, decoder layers,
+        CTC log-probs [S][max_frames][V], per-layer cross K/V [S*max_frames][2D], folded LayerNorms).
+        All zero: an empty slot's rows run through every kernel of a step, on finite values.
+        With `_session_admit` one of the two places where a session touches the engine: the
+        scripted-decoder tests replace both (engine None, no memory, a table decoder), so the real
+        admission path is covered by the model tests only (tests/test_gpu_decode_stream.py)."""
+        eng = self.e2e.engine()
+        if eng.dtype != torch.float32:
+            raise NotImplementedError("decode sessions run on the fp32 engine, the evaluation precision of the "
+                                      "reference; a bf16 engine decodes with decode_batch")
+        dev, D = eng.device, eng.dD
+        logp = torch.zeros(S, max_frames, eng.V, device=dev, dtype=torch.float32)
+        mem = [torch.zeros(S * max_frames, 2 * D, device=dev, dtype=eng.dtype) for _ in range(eng.dl)]
+        fold = self._fold_layernorms(eng) if FOLD_LN and self.use_dec else None
+        return eng, dev, eng.dtype, D, eng.dl, logp, mem, fold
+
+    def _session_admit(self, sess, slot, x):
+        """utterance x (T, d) into slot `slot` of the session, eagerly on the current stream: the
+        launches decode_batch makes per utterance (CTC head and cross-attention K / V projections
+        over its own T rows, log-softmax), written into the slot's regions. (The second hook the
+        scripted-decoder tests replace, see `_session_buffers`.)"""
+        eng, st = sess.eng, sess.st
+        ar, D, Tm = eng.arena, eng.dD, st["Tm"]
+        T = int(x.shape[0])
+        xu, r0 = sess.xbuf[:T], slot * Tm
+        ops.cast(x.to(eng.device).reshape(T, D).contiguous(), xu)
+        cl = sess.clbuf[:T]
+        ops.linear_fwd(xu, eng.w("ctc.ctc_lo.weight"), ar.master("ctc.ctc_lo.bias"), out=cl[:, :eng.V])
+        for i in range(eng.dl):
+            ca = f"decoder.decoders.{i}.src_attn."
+            ops.linear_fwd(xu, ar.span([ca + "linear_k.weight", ca + "linear_v.weight"]),
+                           ar.span([ca + "linear_k.bias", ca + "linear_v.bias"], buf="master"),
+                           out=st["mem"][i][r0:r0 + T])
+        ops.log_softmax_rows(cl, eng.V, st["logp"][slot, :T])
+
+    def _new_stream_state(self, device, dtype, S, max_frames, steps, logp, mem, D, layers, end_detect=1, fold=None):
+        """the search state of a session: `_new_state` of S utterances of max_frames frames and
+        `steps` steps, with every slot empty (done, no live row), the positions per slot (upos)
+        and per row (rowpos; also under "pos", which the step's kernels read), and one more
+        history row: a done slot stands one past its last record and writes there."""
+        st = self._new_state(device, dtype, [max_frames] * S, [steps] * S, logp, mem, D, layers,
+                             end_detect=end_detect, fold=fold)
+        R = st["R"]
+        st["upos"] = torch.zeros(S, device=device, dtype=torch.int32)
+        st["rowpos"] = st["pos"] = torch.zeros(R, device=device, dtype=torch.int32)
+        for k in ("bp_prev", "bp_tok", "end_flag", "end_score", "end_dec", "end_ctc"):
+            st[k] = torch.zeros(steps + 1, R, device=device, dtype=st[k].dtype)
+        for k in ("ids", "klen_self", "src"):
+            st[k].zero_()
+        for k in ("psi", "r_new", "psi_c", "r_scr", "psi_full"):
+            if k in st:
+                st[k].zero_()
+        for t in st["r_prev"]:
+            t.zero_()
+        st["score"].fill_(float("-inf"))
+        st["done"].fill_(1)
+        st["done"][S] = S
+        return st
+
+    def _collect_slot(self, st, slot, n):
+        """`_collect` for one slot whose utterance ended after n steps: its history columns"""
+        beam = self.beam_size
+        ended = [hyp for _, hyp in self._ended_hyps(st, n, slot * beam, beam)]
+        return sorted(ended, key=lambda h: float(h.score), reverse=True)
 
     @staticmethod
     def _make_hyp(hyp, use_dec=True, use_ctc=True):
@@ -418,6 +520,148 @@ class BatchBeamSearch:
             scores["ctc"] = torch.tensor(hyp["ctc"], dtype=torch.float32)
         return Hypothesis(yseq=torch.tensor(hyp["yseq"], dtype=torch.int64),
                           score=torch.tensor(hyp["score"], dtype=torch.float32), scores=scores, states={})
+
+
+class DecodeSession:
+    """A persistent beam-search session over a stream of utterances (continuous batching).
+
+    Geometry fixed at creation: `slots` utterances x beam rows (at most 64 rows, the few-row GEMM's
+    limit), `max_frames` memory frames per slot, Lcap = maxlen(max_frames) + 1 positions. The session
+    owns one search state, the per-slot memory regions (cross-attention K/V per decoder layer,
+    CTC log-probs), the self-attention cache and the two step graphs, captured once. It snapshots
+    the folded LayerNorm weights at creation: weights changed afterwards need a new session.
+
+    Every step is one graph replay, a slot's step 0 included: positions are per row on the device,
+    so one replay is step 0 of a freshly filled slot and step 200 of its neighbour. An utterance
+    is admitted into a free slot eagerly (its memory projections, log-softmax, avsr_beam_slot_reset);
+    every `poll` replays the host reads the per-slot done flags (pinned, non-blocking copy and an
+    event), collects the n-best of each newly finished slot from its history columns and frees it.
+    Per utterance the result equals `bs(x)`: rows never read another slot's state.
+
+    `run(xs)` yields (index, nbest) in completion order; an utterance longer than max_frames is
+    decoded alone through `bs(x)` and delivered in its place. A session runs any number of
+    streams one after another; `close()` drops graphs and buffers."""
+
+    def __init__(self, bs, slots=None, max_frames=375, maxlenratio=0.0, minlenratio=0.0, poll=4, graphs=True):
+        beam = bs.beam_size
+        S = stream_slots.default_slots(beam) if slots is None else int(slots)
+        stream_slots.check_geometry(S, beam)
+        if max_frames < 1 or poll < 1:
+            raise ValueError(f"max_frames = {max_frames}, poll = {poll}")
+        self.bs, self.S, self.max_frames, self.poll = bs, S, int(max_frames), int(poll)
+        self.maxlenratio, self.minlenratio = maxlenratio, minlenratio
+        steps = bs._maxlen(self.max_frames, maxlenratio)
+        if steps < 1:
+            raise ValueError(f"maxlenratio = {maxlenratio}: no step to run")
+        self.eng, dev, dtype, D, layers, logp, mem, fold = bs._session_buffers(S, self.max_frames)
+        self.device = dev
+        if self.eng is not None:
+            self.eng.ensure_pe(steps + 1)
+            self.xbuf = torch.empty(self.max_frames, D, device=dev, dtype=dtype)
+            self.clbuf = torch.zeros(self.max_frames, self.eng.Vp, device=dev, dtype=dtype)
+        self.st = bs._new_stream_state(dev, dtype, S, self.max_frames, steps, logp, mem, D, layers,
+                                       end_detect=int(maxlenratio == 0.0), fold=fold)
+        self.book = None
+        self.k = 0                              # ping-pong buffer the next step reads
+        self.replays = 0                        # steps run so far, over all streams
+        self._host = torch.empty(2 * S + 1, dtype=torch.int32).pin_memory()    # done[S + 1], upos[S]
+        self._event = torch.cuda.Event()
+        self.graphs = bs._capture(self.eng, self.st) if graphs else None
+        self._ws = None
+        if graphs:
+            # what the graphs point into besides the session's own state, kept alive with them: the
+            # capture stream's workspaces and the engine's positional-encoding table (a later, longer
+            # search makes the engine allocate a new table; the graphs go on reading this one, whose
+            # rows are the same values)
+            key = (ops._norm_dev(dev), _capture_stream(dev).cuda_stream)
+            self._ws = (ops._SKINNY_WS.get(key), ops._DA_WS.get(key), None if self.eng is None else self.eng._pe)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        self.graphs = self.st = self._ws = None
+        self.xbuf = self.clbuf = None
+
+    def _step(self):
+        if self.graphs is not None:
+            self.graphs[self.k].replay()
+        else:
+            self.bs._step(self.eng, self.st, False, self.k)
+        self.k ^= 1
+        self.replays += 1
+
+    def _admit(self, slot, x):
+        bs, st = self.bs, self.st
+        T = int(x.shape[0])
+        bs._session_admit(self, slot, x)
+        ops.beam_slot_reset(U=self.S, beam=bs.beam_size, Lmax=st["Lmax"], slot=slot, sos=bs.sos,
+                            maxlen=bs._maxlen(T, self.maxlenratio), tlen=T, upos=st["upos"], rowpos=st["rowpos"],
+                            done=st["done"], tok=st["tok"], score=st["score"], sdec=st["sdec"], sctc=st["sctc"],
+                            s_prev=st["s_prev"], best_len=st["best_len"], best_end=st["best_end"],
+                            maxlen_arr=st["maxlen"], tlen_arr=st["tlen"], klen_mem=st["klen_mem"])
+
+    def _poll(self):
+        """(done per slot, position per slot) as of the steps issued so far"""
+        S, st = self.S, self.st
+        self._host[:S + 1].copy_(st["done"], non_blocking=True)
+        self._host[S + 1:].copy_(st["upos"], non_blocking=True)
+        self._event.record()
+        self._event.synchronize()
+        h = self._host.tolist()
+        return h[:S], h[S + 1:]
+
+    def run(self, xs):
+        """generator of (index, nbest) in completion order for the encoded utterances xs (an
+        iterable, consumed as slots become free)"""
+        if self.st is None:
+            raise RuntimeError("the session is closed")
+        bs = self.bs
+        book = self.book = stream_slots.SlotBook(self.S, bs.beam_size, self.max_frames)   # (kept for inspection)
+        inputs = enumerate(xs)
+        held, limit, ran = {}, {}, {}           # per busy slot: its input, its maxlen, its steps so far
+        budget, start, since, more = 0, self.replays, 0, True
+        while True:
+            while more and book.free_slot() is not None:
+                nxt = next(inputs, None)
+                if nxt is None:
+                    more = False
+                    break
+                i, x = nxt
+                if not book.fits(int(x.shape[0])):      # oversize: the one-utterance search, in its place
+                    yield book.bypass(i), bs.forward(x, self.maxlenratio, self.minlenratio)
+                    continue
+                slot = book.admit(i, int(x.shape[0]))
+                self._admit(slot, x)
+                held[slot], limit[slot], ran[slot] = x, bs._maxlen(int(x.shape[0]), self.maxlenratio), 0
+                budget += limit[slot]
+            busy = book.busy()
+            if not busy:
+                break
+            if self.replays - start >= budget + self.poll:
+                raise RuntimeError(f"decode session: {self.replays - start} steps for a budget of {budget}")
+            self._step()
+            since += 1
+            for slot in busy:
+                ran[slot] += 1
+            # nothing can have ended before its first `poll`-th step unless a slot is at its limit
+            if since < self.poll and not any(ran[s] >= limit[s] for s in busy):
+                continue
+            since = 0
+            done, upos = self._poll()
+            for slot in sorted(busy):
+                if not done[slot]:
+                    if ran[slot] >= limit[slot]:
+                        raise RuntimeError(f"decode session: slot {slot} not done after its {limit[slot]} steps")
+                    continue
+                nbest = bs._collect_slot(self.st, slot, min(upos[slot], limit[slot]))
+                x = held.pop(slot)
+                if not nbest and self.minlenratio >= 0.1:
+                    nbest = bs.forward(x, self.maxlenratio, max(0.0, self.minlenratio - 0.1))
+                yield book.finish(slot), nbest
 
 
 def get_beam_search_decoder(model, token_list, ctc_weight=0.1, beam_size=3):

@@ -68,12 +68,17 @@ def gather_to_rank0(local, world):
     return [r for _, r in sorted((t for p in parts for t in p), key=lambda t: t[0])]
 
 
-def run_sharded(units, infer, rank=0, world=1, infer_batch=None, batch=8):
+def run_sharded(units, infer, rank=0, world=1, infer_batch=None, batch=8, infer_stream=None):
     """decode this rank's share with `infer(unit) -> text` (or `infer_batch(list of units) ->
-    texts`, `batch` units at a time: the engine's batched beam search); rank 0 returns all
-    texts in unit order."""
+    texts`, `batch` units at a time: the engine's batched beam search; or `infer_stream(iterable
+    of units) -> iterator of (position in the iterable, text)` in any order: a decode session
+    that refills its slots, decode.DecodeSession.run); rank 0 returns all texts in unit order."""
     mine = shard(units, rank, world)
-    if infer_batch is None:
+    if infer_stream is not None:
+        local = sorted((mine[p][0], text) for p, text in infer_stream(u for _, u in mine))
+        if [i for i, _ in local] != [i for i, _ in mine]:
+            raise RuntimeError("infer_stream must deliver every unit exactly once")
+    elif infer_batch is None:
         local = [(i, infer(u)) for i, u in mine]
     else:
         local = []

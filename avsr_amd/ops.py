@@ -106,6 +106,15 @@ def reserve_stream_workspaces(device, dec_attn_floats=0):
         _DA_WS[key] = torch.empty(dec_attn_floats, device=device, dtype=torch.float32)
 
 
+def _pos_stride(pos, rows, per_row):
+    """stride of a device position argument: int32 [1] shared by every row (0), or, when the
+    caller says `per_row`, int32 [rows] with one position per row (1: the rowpos of a decode
+    session). The caller states which; it is never guessed from the size, since a session of one
+    row has both sizes at once and its "first step is a property of the row" rule needs stride 1."""
+    assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.numel() >= (rows if per_row else 1)
+    return 1 if per_row else 0
+
+
 def gemm(A, B, C, *, M, N, K, a_kmajor, b_kmajor, lda, ldb, ldc, batch=1,
          strideA=0, strideB=0, strideC=0, alpha=1.0, beta=0.0, bias=None, act=L.ACT_NONE,
          epi_bwd=False, preact=None, res=None, ldr=None, strideR=0, gate=None, drop_p=0.0, seed=0,
@@ -152,10 +161,11 @@ def gemm(A, B, C, *, M, N, K, a_kmajor, b_kmajor, lda, ldb, ldc, batch=1,
     if ln_c1 is not None:
         assert ln_c1.dtype == torch.float32 and ln_c1.numel() >= N and dt == L.AVSR_F32
         p.ln_c1, p.ln_eps = ln_c1.data_ptr(), float(ln_eps)
-    if kv is not None:           # (k cache, v cache, device position, rows per step)
-        kc, vc, pos, rows = kv
+    if kv is not None:           # (k cache, v cache, device position, rows per step[, per_row: positions [M]])
+        kc, vc, pos, rows = kv[:4]
         assert kc.dtype == vc.dtype == torch.float32 and pos.dtype == torch.int32 and dt == L.AVSR_F32
         p.kv_k, p.kv_v, p.kv_pos, p.kv_rows = kc.data_ptr(), vc.data_ptr(), pos.data_ptr(), int(rows)
+        p.kv_pos_stride = _pos_stride(pos, M, len(kv) > 4 and bool(kv[4]))
     if db is not None:
         assert db.dtype == torch.float32 and db.numel() >= N and db_ws is not None and db_ws.dtype == torch.float32
         assert db_ws.numel() >= ((M + 63) // 64) * N
@@ -844,12 +854,13 @@ def mask_rows(x, B, T, lengths):
     return x
 
 
-def embed_fwd(tok, table, pe, scale, y, L_, drop_p=0.0, seed=0, pe_row=None):
+def embed_fwd(tok, table, pe, scale, y, L_, drop_p=0.0, seed=0, pe_row=None, per_row=False):
     """pe_row: optional device int32 [1]: every row adds pe[pe_row[0]] (a beam-search step's
-    position kept on the device)"""
+    position kept on the device); with per_row int32 [rows]: row r adds pe[pe_row[r]] (a decode session)"""
     _call("avsr_embed_fwd", L.fill(L.EmbedParams, dtype=dtype_code(table), rows=tok.shape[0], L=L_,
                                     D=table.shape[1], tok=tok, table=table, pe=pe, scale=scale, y=y,
-                                    drop_p=float(drop_p), seed=int(seed) & (2 ** 64 - 1), pe_row=pe_row))
+                                    drop_p=float(drop_p), seed=int(seed) & (2 ** 64 - 1), pe_row=pe_row,
+                                    pe_row_stride=0 if pe_row is None else _pos_stride(pe_row, tok.shape[0], per_row)))
     return y
 
 
@@ -1041,15 +1052,17 @@ def log_softmax_topk(x, V, out, K, ids):
 
 
 def ctc_prefix(logp, r_prev, last, ids, r_new, psi, *, n, out_len, blank, eos, uidx=None, tlen=None,
-               out_len_dev=None):
+               out_len_dev=None, per_row=False):
     """logp (T, V) of one utterance, or (U, Tmax, V) with uidx (per-hypothesis utterance) and
     tlen (per-utterance frames) for batched decoding; out_len_dev: device int32 [1] overriding
-    out_len (graph-captured steps)"""
+    out_len (graph-captured steps), or with per_row int32 [n], one length per hypothesis row (a
+    decode session): there a row of length 0 is at its first step whatever r_prev holds"""
     T, V = logp.shape[-2:]
     _call("avsr_ctc_prefix", L.fill(L.CtcPrefixParams, n=n, T=T, V=V, P=ids.shape[1], blank=blank, eos=eos,
                                      out_len=out_len, logp=logp, r_prev=r_prev, last=last, ids=ids, r_new=r_new,
                                      psi=psi, uidx=uidx, logp_ustride=T * V if uidx is not None else 0,
-                                     tlen=tlen, out_len_dev=out_len_dev))
+                                     tlen=tlen, out_len_dev=out_len_dev,
+                                     out_len_stride=0 if out_len_dev is None else _pos_stride(out_len_dev, n, per_row)))
 
 
 def beam_select(dec, V, ids, psi, s_prev, score, out, *, n, beam, blank, eos, w_dec, w_ctc, seg=None):
@@ -1070,18 +1083,36 @@ def gather_rows(src, dst, idx, *, groups, n, row_bytes, src_gstride, src_rstride
                                       dst_gstride, dst_rstride, idx.data_ptr(), L.stream_ptr()), "avsr_gather_rows")
 
 
-def beam_step_prep(R, pos, anc, klen):
-    """anc[r][pos] = pos*R + r, klen[r] = pos + 1 (pos: device int32 [1]); avsr_hip.h"""
-    L.check(L.load().avsr_beam_step_prep(R, anc.shape[1], pos.data_ptr(), anc.data_ptr(), klen.data_ptr(),
-                                         L.stream_ptr()), "avsr_beam_step_prep")
+def beam_step_prep(R, pos, anc, klen, per_row=False):
+    """anc[r][pos] = pos*R + r, klen[r] = pos + 1 (pos: device int32 [1], or with per_row [R],
+    one position per row); avsr_hip.h"""
+    lib = L.load()
+    fn, name = ((lib.avsr_beam_step_prep_rows, "avsr_beam_step_prep_rows") if _pos_stride(pos, R, per_row) else
+                (lib.avsr_beam_step_prep, "avsr_beam_step_prep"))
+    L.check(fn(R, anc.shape[1], pos.data_ptr(), anc.data_ptr(), klen.data_ptr(), L.stream_ptr()), name)
 
 
-def beam_kv_put(qkv, cache_k, cache_v, pos, R, D):
-    """this step's self-attention K / V rows -> cache rows pos*R + r"""
-    L.check(L.load().avsr_beam_kv_put(dtype_code(qkv), R, D, qkv.data_ptr(), qkv.stride(0), cache_k.data_ptr(),
-                                      cache_v.data_ptr(), pos.data_ptr(), L.stream_ptr()), "avsr_beam_kv_put")
+def beam_kv_put(qkv, cache_k, cache_v, pos, R, D, per_row=False):
+    """this step's self-attention K / V rows -> cache rows pos*R + r (pos: device int32 [1], or
+    with per_row [R], one position per row)"""
+    lib = L.load()
+    fn, name = ((lib.avsr_beam_kv_put_rows, "avsr_beam_kv_put_rows") if _pos_stride(pos, R, per_row) else
+                (lib.avsr_beam_kv_put, "avsr_beam_kv_put"))
+    L.check(fn(dtype_code(qkv), R, D, qkv.data_ptr(), qkv.stride(0), cache_k.data_ptr(), cache_v.data_ptr(),
+               pos.data_ptr(), L.stream_ptr()), name)
 
 
 def beam_post(**kw):
     """device-side bookkeeping after avsr_beam_select (avsr_hip.h avsr_beam_post)"""
     _call("avsr_beam_post", L.fill(L.BeamPostParams, **kw))
+
+
+def beam_slot_reset(*, U, beam, Lmax, slot, sos, maxlen, tlen, upos, rowpos, done, tok, score, sdec, sctc, s_prev,
+                    best_len, best_end, maxlen_arr, tlen_arr, klen_mem):
+    """slot `slot` of a decode session back to the state of a fresh utterance of `tlen` frames and
+    `maxlen` steps (avsr_hip.h avsr_beam_slot_reset); only that slot's rows are written"""
+    _call("avsr_beam_slot_reset", L.fill(L.BeamSlotResetParams, U=U, beam=beam, R=U * beam, Lmax=Lmax, slot=int(slot),
+                                          sos=sos, maxlen=int(maxlen), tlen=int(tlen), upos=upos, rowpos=rowpos,
+                                          done=done, tok=tok, score=score, sdec=sdec, sctc=sctc, s_prev=s_prev,
+                                          best_len=best_len, best_end=best_end, maxlen_arr=maxlen_arr,
+                                          tlen_arr=tlen_arr, klen_mem=klen_mem))

@@ -174,6 +174,9 @@ typedef struct {
                                 The caller zeroes them once; every launch leaves them zero. Launches
                                 that share a counter buffer must be ordered (one stream). NULL: a
                                 separate reduction pass. */
+  int kv_pos_stride;         /* KV-cache append: 0 = one shared position *kv_pos (above); 1 = one
+                                position per row, row m appends at cache row kv_pos[m] * kv_rows + m
+                                (the rows of a decode session stand at different steps) */
 } avsr_gemm_params;
 #define AVSR_GEMM_COLSUM_WS(M, N) ((int64_t)(((M) + 63) / 64) * (N))
 /* slabs are AVSR_GEMM_SLAB_PAD floats apart beyond M*N: power-of-two slab strides put the
@@ -674,6 +677,7 @@ typedef struct {
   const void* dy; float* dtable;
   const int* pe_row;         /* forward, optional: device int, every row adds pe[pe_row[0]] (L ignored):
                                 the position of a beam-search step kept on the device */
+  int pe_row_stride;         /* 0: the one shared position above; 1: row r adds pe[pe_row[r]] */
 } avsr_embed_params;
 int avsr_embed_fwd(const avsr_embed_params* p, void* stream);
 int avsr_embed_bwd(const avsr_embed_params* p, void* stream);
@@ -739,6 +743,8 @@ int avsr_adamw(const avsr_adamw_params* p, void* stream);
  *   last[h], CTC forward variables r_prev[h][T][2] or NULL at the first step) and its P
  *   scored tokens ids[h][:]: r_new[h][j][T][2] and psi[h][j] = log prefix probability
  *   (LOGZERO for blank, r_sum[T-1] for eos), psi[h][P] = r_sum[T-1] (the eos score).
+ *   A prefix longer than the utterance (out_len > T: a dead row of a search that runs past its
+ *   frames) is scored as one of length T: both kernels keep every frame index below T.
  * avsr_beam_select: weighted[h][v] = w_dec*dec[h][v] + w_ctc*(psi(h,v) - s_prev[h]) +
  *   score[h]; the beam best (h, v) in descending order -> out_prev/out_tok/out_score,
  *   out_dec = dec[h][v], out_ctc = psi - s_prev, out_s = psi, out_col = column of v in
@@ -808,6 +814,11 @@ typedef struct {
    * (<= T, the row stride of r_prev / r_new) */
   const int* uidx; int64_t logp_ustride; const int* tlen;
   const int* out_len_dev;     /* optional device int overriding out_len (graph-captured steps) */
+  int out_len_stride;         /* 0: out_len_dev is one shared int; 1: one length per hypothesis row,
+                                 out_len_dev[h]. In that form a row of length 0 computes what a launch
+                                 with r_prev == NULL computes (the blank cumulative sum as the previous
+                                 state, r0(0) = logp[id]) whatever r_prev holds: "first step" is a
+                                 property of the row, not of the launch */
 } avsr_ctc_prefix_params;
 int avsr_ctc_prefix(const avsr_ctc_prefix_params* p, void* stream);
 
@@ -844,7 +855,21 @@ int avsr_gather_rows(int groups, int n, int64_t row_bytes, const void* src, int6
  *   score, decoder / CTC score sums in double like the reference's Python floats, CTC prefix
  *   score), the back-pointers and ended-hypothesis records of the step, per-utterance end
  *   detection (e2e_asr_common.py:18-48 over the per-length best ended scores) and stop rules;
- *   src[0..R) = rows to gather the ancestry from, src[R..2R) = r_new rows for r_prev; *pos += 1. */
+ *   src[0..R) = rows to gather the ancestry from, src[R..2R) = r_new rows for r_prev; *pos += 1.
+ * Positions per row (a decode session, avsr_amd.decode.DecodeSession: a fixed number of utterance
+ * slots, a finished utterance's slot refilled while the others keep stepping, so one replayed step
+ * is step 0 of one slot and step 200 of another). upos[U] is the position of each slot and
+ * rowpos[R] the same per row, rowpos[r] = upos[r / beam]:
+ * avsr_beam_step_prep_rows / avsr_beam_kv_put_rows: the two kernels above with pos = rowpos[r].
+ * avsr_beam_post with upos != NULL (`pos` unused): pos = upos[u] everywhere (history index
+ *   pos*R + r, forced eos at maxlen[u] - 1, hypothesis length of end detection, best_len); a slot
+ *   that was done before the step keeps its position, every other advances by one (also on the
+ *   step that finishes it, so a done slot stands one past its last record); rowpos is rewritten.
+ *   A done slot's history writes go to its frozen position: the history needs max(maxlen) + 1 rows.
+ * avsr_beam_slot_reset: slot u back to the state of a fresh utterance (upos 0, done 0, tok sos,
+ *   score 0 for its first row and -inf for the others, sdec = sctc = s_prev = 0, best_len row and
+ *   best_end -inf, maxlen / tlen / klen_mem from the arguments, done[U] recounted); touches only
+ *   that slot's rows. */
 typedef struct {
   int U, beam, P, R, Lmax, steps_cap, eos, end_detect;
   double d_end;
@@ -858,7 +883,21 @@ typedef struct {
   float* best_len;           /* [U][Lmax + 3] */
   float* best_end;           /* [U] */
   int* done;                 /* [U + 1]: per utterance, then the count */
+  int* upos;                 /* [U] or NULL: per-slot positions (see above) */
+  int* rowpos;               /* [R], with upos */
 } avsr_beam_post_params;
+typedef struct {
+  int U, beam, R, Lmax, slot, sos;
+  int maxlen, tlen;          /* the new utterance's step limit and frames (>= 1) */
+  int* upos; int* rowpos; int* done;
+  int* tok; float* score; double* sdec; double* sctc; float* s_prev;
+  float* best_len; float* best_end;
+  int* maxlen_arr; int* tlen_arr; int* klen_mem;
+} avsr_beam_slot_reset_params;
+int avsr_beam_step_prep_rows(int R, int Lmax, const int* rowpos, int* anc, int* klen, void* stream);
+int avsr_beam_kv_put_rows(int dtype, int R, int D, const void* qkv, int64_t ldqkv, void* cache_k, void* cache_v,
+                          const int* rowpos, void* stream);
+int avsr_beam_slot_reset(const avsr_beam_slot_reset_params* p, void* stream);
 int avsr_beam_step_prep(int R, int Lmax, const int* pos, int* anc, int* klen, void* stream);
 int avsr_beam_kv_put(int dtype, int R, int D, const void* qkv, int64_t ldqkv, void* cache_k, void* cache_v,
                      const int* pos, void* stream);
