@@ -254,46 +254,20 @@ static inline int avsr_grid(long work, int per_block = 256, int cap = 2048) {
   return (int)(g < cap ? g : cap);
 }
 
-// Column sums of a row-block partial workspace: out[c] += sum_b ws[b*ld + c] for c < N, or,
-// when out1 != nullptr, columns [N1, N) go to out1[c - N1] (LayerNorm dgamma/dbeta in one
-// launch). Block = 32 columns (one 128-byte line per row) x 32 row lanes (1024 threads): each
-// thread adds nb/32 partial rows with four independent accumulators, then the row lanes are
-// summed in a fixed order (deterministic). (8 row lanes: ~6.7 us per 256 x 1024 workspace,
-// a latency-bound chain of 32 loads per thread.)
-constexpr int COLSUM_THREADS = 1024;
-AVSR_DEV void colsum_block(const float* ws, int nb, int64_t ld, int N, float* out, int N1, float* out1, int cb) {
-  __shared__ float red[32][33];
-  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-  const int c = cb * 32 + cl;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (c < N) {
-    int b = rl;
-    for (; b + 96 < nb; b += 128) {
-      s0 += ws[(int64_t)b * ld + c];
-      s1 += ws[(int64_t)(b + 32) * ld + c];
-      s2 += ws[(int64_t)(b + 64) * ld + c];
-      s3 += ws[(int64_t)(b + 96) * ld + c];
-    }
-    for (; b < nb; b += 32) s0 += ws[(int64_t)b * ld + c];
-  }
-  red[rl][cl] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (rl == 0 && c < N) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 32; ++i) s += red[i][cl];
-    if (out1 && c >= N1) out1[c - N1] += s;
-    else out[c] += s;
-  }
+// Two-way dtype dispatch of an entry point: calls f with a value of the element type (bf16 or
+// float; take it as `auto t` and name the type `decltype(t)`) and returns what f returns, or
+// AVSR_E_DTYPE for any other code without calling f. Entry points wrap all their work in f, so
+// the dtype is checked before any size early-out or launch.
+template <typename F>
+int avsr_by_dtype(int dtype, F&& f) {
+  if (dtype == AVSR_BF16) return f(bf16{});
+  if (dtype == AVSR_F32) return f(float{});
+  return AVSR_E_DTYPE;
 }
-static __global__ __launch_bounds__(COLSUM_THREADS) void colsum_finalize_kernel(const float* ws, int nb, int64_t ld, int N,
-                                                                                 float* out, int N1, float* out1) {
-  colsum_block(ws, nb, ld, N, out, N1, out1, blockIdx.x);
-}
-static inline dim3 colsum_grid(int N) { return dim3((N + 31) / 32); }
 
 // The row-block partial workspaces of bias / LayerNorm parameter gradients are finalised by
-// colsum_launch: at once, or — between avsr_colsum_defer(1) and avsr_colsum_flush() — queued
-// host-side and reduced by ONE batched launch per flush (misc.hip). Callers keep the
-// workspaces alive until the flush.
+// colsum_launch: out[c] += sum_b ws[b*ld + c] for c < N, or, when out1 != nullptr, columns
+// [N1, N) go to out1[c - N1] (LayerNorm dgamma/dbeta in one launch). At once, or — between
+// avsr_colsum_defer(1) and avsr_colsum_flush() — queued host-side and reduced by ONE batched
+// launch per flush (colsum.hip). Callers keep the workspaces alive until the flush.
 int colsum_launch(const float* ws, int nb, int64_t ld, int N, float* out, int N1, float* out1, hipStream_t st);

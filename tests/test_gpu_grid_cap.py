@@ -13,24 +13,24 @@ Audit of every avsr_grid( / bn_grid( call site (items = work items of one launch
 training step at B = 16, T = 375, 6000 frames, bf16; beam-5 = 16 utterances x 5 hypotheses):
 
 call site                                  cap (items)   workload (items)              covering test
-norm.hip   bn_act_fwd                      524,288       23.2 M (C2 stage 1)           test_bn_chain_* (here)
-norm.hip   bn_act_bwd_reduce               524,288       23.2 M                        test_bn_chain_* (here)
-norm.hip   bn_bwd_apply                    524,288       23.2 M                        test_bn_chain_* (here)
-norm.hip   stem_pool_fwd (2x2 blocks)      524,288       5.8 M                         test_stem_pool_fwd_above_cap (here)
-norm.hip   stem_pool_bwd_apply (2x2)       524,288       23.2 M                        test_stem_bwd_apply_above_cap[block12] (here)
-norm.hip   stem_pool_bwd_apply (pixel)     524,288       odd frame sizes only          test_stem_bwd_apply_above_cap[pixel*] (here)
-norm.hip   avgpool_fwd                     524,288       384,000 (fp32: 768,000)       test_avgpool_above_cap (here)
-norm.hip   avgpool_bwd                     524,288       3.46 M                        test_avgpool_above_cap (here)
-misc.hip   mask_rows                       524,288       768,000 (16 x 375 x 1024)     test_mask_rows_above_cap (here)
-misc.hip   embed_fwd                       524,288       token rows x 128: below the   below the cap; test_gpu_loss_misc (direct)
+batchnorm.hip bn_act_fwd                   524,288       23.2 M (C2 stage 1)           test_bn_chain_* (here)
+batchnorm.hip bn_act_bwd_reduce            524,288       23.2 M                        test_bn_chain_* (here)
+batchnorm.hip bn_bwd_apply                 524,288       23.2 M                        test_bn_chain_* (here)
+pool.hip stem_pool_fwd (2x2 blocks)        524,288       5.8 M                         test_stem_pool_fwd_above_cap (here)
+pool.hip stem_pool_bwd_apply (2x2)         524,288       23.2 M                        test_stem_bwd_apply_above_cap[block12] (here)
+pool.hip stem_pool_bwd_apply (pixel)       524,288       odd frame sizes only          test_stem_bwd_apply_above_cap[pixel*] (here)
+pool.hip avgpool_fwd                       524,288       384,000 (fp32: 768,000)       test_avgpool_above_cap (here)
+pool.hip avgpool_bwd                       524,288       3.46 M                        test_avgpool_above_cap (here)
+elementwise.hip mask_rows                  524,288       768,000 (16 x 375 x 1024)     test_mask_rows_above_cap (here)
+elementwise.hip embed_fwd                  524,288       token rows x 128: below the   below the cap; test_gpu_loss_misc (direct)
                                                          cap up to 4096 rows (C2: 16 x
                                                          label length; beam-5: 10,240)
-misc.hip   audio_pack                      524,288       624,000 (16 x 104 x 375)      test_audio_pack_above_cap (here)
-misc.hip   weightnorm_fwd (wn_apply)       524,288       8.4 M (1024 x 128 x 64)       test_gpu_loss_misc::test_weightnorm[1024-128-64]
-misc.hip   weightnorm_bwd (wn_bwd)         524,288       8.4 M                         test_gpu_loss_misc::test_weightnorm[1024-128-64]
-misc.hip   sumsq                           262,144 x4    the gradient arena, 10^8      test_sumsq_above_cap (here; the existing
+elementwise.hip audio_pack                 524,288       624,000 (16 x 104 x 375)      test_audio_pack_above_cap (here)
+param.hip weightnorm_fwd (wn_apply)        524,288       8.4 M (1024 x 128 x 64)       test_gpu_loss_misc::test_weightnorm[1024-128-64]
+param.hip weightnorm_bwd (wn_bwd)          524,288       8.4 M                         test_gpu_loss_misc::test_weightnorm[1024-128-64]
+param.hip sumsq                            262,144 x4    the gradient arena, 10^8      test_sumsq_above_cap (here; the existing
                                                                                        3,000,003-element call feeds only the clip)
-misc.hip   adamw                           1,048,576 x4  the arena in slices; the      test_gpu_loss_misc::
+param.hip adamw                            1,048,576 x4  the arena in slices; the      test_gpu_loss_misc::
                                            or max_blocks overlapped update caps at     test_adamw_grid_cap_bit_identical (caps 64, 512
                                                          max_blocks                    against the uncapped grid, bit for bit)
 frontend.hip video_normalize               1,048,576 x4  11.6 M (6000 x 88 x 22)       test_video_normalize_above_cap (here)
@@ -45,7 +45,7 @@ attention.hip attn_bwd_prep                524,288       96,000 (16 x 375 x 16) 
 conv.hip   stem weight-grad reduce         262,144 x4    6,272 x4 (64 x 392)           below the cap; test_gpu_conv (stem weight gradient)
 conv.hip   conv weight-grad slab reduce    262,144 x4    589,824 x4 (3 x 3 x 512 x     test_gpu_conv (weight gradient at 3 x 3 x 512 x 512)
                                                          512)
-common.h   avsr_grid itself / norm.hip bn_grid: the helpers.
+common.h   avsr_grid itself / norm.h bn_grid: the helpers.
 """
 import math
 

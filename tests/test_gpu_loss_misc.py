@@ -214,6 +214,17 @@ def test_stem_as_2d_conv(dev, dtype):
     assert _rel(gw, wr.grad) < (1e-4 if dtype == torch.float32 else 2e-2)
 
 
+def test_stem_wpack_rejects_unknown_dtype(dev):
+    """avsr_stem_wpack has a fixed size, so the no-GPU table of test_lib_abi.py (calls over
+    nothing, without pointers) cannot hold it: with real buffers, an unknown dtype code is
+    AVSR_E_DTYPE (1003) and nothing is written"""
+    w = torch.randn(64, 1, 5, 7, 7, device=dev)
+    wp = torch.full((64, 7, 7, 8), float("nan"), device=dev)
+    assert L.load().avsr_stem_wpack(7, w.data_ptr(), wp.data_ptr(), L.stream_ptr()) == 1003
+    torch.cuda.synchronize()
+    assert torch.isnan(wp).all()
+
+
 @pytest.mark.parametrize("O,K,C", [(96, 16, 8), (1024, 128, 64), (40, 6, 6)])
 def test_weightnorm(dev, O, K, C):
     """weight norm over dims (0, 1) of the torch (out, in/groups, k) weight: vectorised

@@ -18,9 +18,16 @@ def _tol(dtype, f32=2e-5, b16=2e-2):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("N,eps,rows", [(1024, 1e-5, 777), (2048, 1e-5, 777), (256, 1e-12, 777), (1024, 1e-5, 3001)])
+@pytest.mark.parametrize("N,eps,rows", [(1024, 1e-5, 777), (2048, 1e-5, 777), (256, 1e-12, 777), (1024, 1e-5, 3001),
+                                        (8, 1e-5, 1), (200, 1e-5, 3), (512, 1e-5, 4), (776, 1e-5, 5), (1544, 1e-5, 9)])
 def test_layernorm(dev, dtype, N, eps, rows):
-    """rows = 3001: each of the backward's 1024 waves walks 2-3 rows through both register stages"""
+    """rows = 3001: the backward's grid is at its cap of 256 blocks and each of its 1024 waves
+    walks 2-3 rows. The small shapes are the edges of the launcher and of the vectors-per-lane
+    (VPL) ladder: (8, 1) one live lane (bf16) and every other lane's load clamped to column
+    N - VE = 0; (200, 3) fewer rows than a block has waves and a partial last stripe of 64 lanes
+    at VPL 1; (512, 4) fp32 at VPL 2; (776, 5) bf16 VPL 2 / fp32 VPL 4 and (1544, 9) bf16 VPL 4 /
+    fp32 VPL 8, each with a partial last stripe, the latter on a grid of three blocks. Fewer rows
+    and columns accumulate less error than the shapes the tolerances were set for."""
     g = torch.Generator().manual_seed(N)
     x = torch.randn(rows, N, generator=g) * 2 + 0.5
     gam = 1 + 0.1 * torch.randn(N, generator=g)
@@ -42,11 +49,12 @@ def test_layernorm(dev, dtype, N, eps, rows):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("p", [0.0, 0.1])
-def test_layernorm_bwd_fused_dropout_bias(dev, dtype, p):
+@pytest.mark.parametrize("rows,N", [(613, 1024), (5, 200)])
+def test_layernorm_bwd_fused_dropout_bias(dev, dtype, p, rows, N):
     """The residual-branch dropout backward + bias gradient fused into the LayerNorm backward
-    (engine._ln_bwd ew=...) equals LayerNorm backward followed by ew_bwd, bit for bit."""
+    (engine._ln_bwd ew=...) equals LayerNorm backward followed by ew_bwd, bit for bit.
+    (5, 200): two blocks, the second with one live wave, and a partial stripe of lanes."""
     g = torch.Generator().manual_seed(11)
-    rows, N = 613, 1024
     x = (torch.randn(rows, N, generator=g) * 2 + 0.5).to(dev, dtype)
     gam = (1 + 0.1 * torch.randn(N, generator=g)).to(dev)
     bet = (0.1 * torch.randn(N, generator=g)).to(dev)

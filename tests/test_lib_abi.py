@@ -218,6 +218,53 @@ def test_conv_path_table():
     assert lib.avsr_conv_path(None, 0) == 1004
 
 
+def _zero_size_calls(dt):
+    """(entry point, arguments) for the LayerNorm, BatchNorm, pooling, elementwise, packing and
+    weight-norm entry points that take a dtype code: every call describes zero rows / images /
+    elements with valid channel counts and strides, and holds no pointer"""
+    ref = ctypes.byref
+    ln = L.fill(L.LayerNormParams, dtype=dt, rows=0, N=64, ldx=64, ldy=64, lddy=64, lddx=64)
+    bn = L.fill(L.BnActParams, dtype=dt, M=0, C=64)
+    sp = L.fill(L.StemPoolParams, dtype=dt, nimg=0, H=4, W=4, C=64, Ho=2, Wo=2)
+    ew = L.fill(L.EwParams, dtype=dt, rows=0, N=64, lddy=64, ldout=64, alpha=1.0)
+    em = L.fill(L.EmbedParams, dtype=dt, rows=0, L=1, D=64)
+    return [
+        ("avsr_layernorm_fwd", (ref(ln), None)),
+        ("avsr_layernorm_bwd", (ref(ln), None)),
+        ("avsr_bn_act_fwd", (ref(bn), None)),
+        ("avsr_bn_act_bwd_reduce", (ref(bn), None)),
+        ("avsr_bn_bwd_apply", (ref(bn), None)),
+        ("avsr_stem_pool_fwd", (ref(sp), None)),
+        ("avsr_stem_pool_bwd_apply", (ref(sp), None)),
+        ("avsr_avgpool_fwd", (dt, 0, 1, 64, None, None, None)),
+        ("avsr_avgpool_bwd", (dt, 0, 1, 64, None, None, None)),
+        ("avsr_ew_bwd", (ref(ew), None)),
+        ("avsr_dropout_fwd", (ref(ew), None)),
+        ("avsr_mask_rows", (dt, 0, 1, 64, None, 64, None, None)),
+        ("avsr_embed_fwd", (ref(em), None)),
+        ("avsr_embed_bwd", (ref(em), None)),
+        ("avsr_stem_pack", (dt, 0, 0, None, None, None)),
+        ("avsr_audio_pack", (dt, 0, 1, 1, None, None, None)),
+        ("avsr_weightnorm_fwd", (dt, 0, 0, 0, None, None, None, None, None)),
+    ]
+
+
+def test_dtype_checked_first():
+    """An unknown dtype code is AVSR_E_DTYPE (1003) before anything else an entry point does: the
+    zero-size early return, the argument checks that need a pointer, any launch. The calls are
+    over nothing and hold no pointers, so an entry point that got the order wrong returns 0 or
+    another code, or launches over nothing; it never reads through a bad pointer. Only the null
+    check of the params struct itself precedes the dtype (it has to). avsr_stem_wpack is not in
+    the table: its size is fixed, so it cannot be called over nothing without pointers; with
+    device buffers it is in test_gpu_loss_misc.py::test_stem_wpack_rejects_unknown_dtype.
+    No GPU."""
+    lib = L.load()
+    for name, args in _zero_size_calls(7):
+        assert getattr(lib, name)(*args) == 1003, name
+    for name in ("avsr_layernorm_fwd", "avsr_bn_act_fwd", "avsr_stem_pool_fwd", "avsr_ew_bwd", "avsr_embed_fwd"):
+        assert getattr(lib, name)(None, None) == 1004, name                 # AVSR_E_ARG: no params
+
+
 def _header_option_defaults():
     """{AVSR_OPT_name: default} from the bracketed defaults in avsr_hip.h's option table"""
     src = open(os.path.join(ROOT, "include", "avsr_hip.h")).read()

@@ -1,9 +1,10 @@
 """Compare the kernels of device assembly files (hipcc --cuda-device-only -S) after a source move:
 python tools/isa_diff.py parent.s new_a.s [new_b.s ...]. Kernels are matched by demangled name with
 the namespaces given by --ns (default: the anonymous one, attn, f32, conv) dropped, and a parent's
-K<float>(..) with a new plain K(..); a body is its text from the label to .Lfunc_end with comments stripped, local
-labels renumbered and other symbols' names blanked; the resources are its .amdhsa_ lines. A kernel that
-several new files hold (a static __global__ of a shared header) is compared once per copy."""
+kernel with the new one that dropped template arguments of one value (RENAMES); a body is its text
+from the label to .Lfunc_end with comments stripped, local labels renumbered and other symbols' names
+blanked; the resources are its .amdhsa_ lines. A kernel that several new files hold (a static
+__global__ of a shared header) is compared once per copy. Several parent files: concatenate them."""
 import argparse
 import re
 import subprocess
@@ -49,12 +50,21 @@ def load(paths, ns):
     return out
 
 
+# a parent kernel that lost template arguments which had one value: (pattern, its new name)
+RENAMES = [
+    (r"^(\w+)<float>\(", r"\1("),                                 # K<float>(..) became a plain K(..)
+    (r"^(stem_bwd_apply2_kernel<\w+), 1>", r"\1>"),                # <T, U = 1> -> <T>
+]
+
+
 def untemplated(old, new):
-    """parent kernels whose one instantiation K<float>(..) became a plain K(..): under the new name"""
+    """parent kernels whose name matches a RENAMES pattern and exists only in its new form: under the new name"""
     for key in [k for k in old if k not in new]:
-        plain = re.sub(r"^(\w+)<float>\(", r"\1(", key)
-        if plain != key and plain in new and plain not in old:
-            old[plain] = old.pop(key)
+        for pat, repl in RENAMES:
+            short = re.sub(pat, repl, key)
+            if short != key and short in new and short not in old:
+                old[short] = old.pop(key)
+                break
 
 
 def main():
