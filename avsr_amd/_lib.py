@@ -223,6 +223,15 @@ class BeamSelectParams(ctypes.Structure):
         ("dec", _c_p), ("ld", _i64), ("ids", _c_p), ("psi", _c_p), ("s_prev", _c_p), ("score", _c_p),
         ("out_prev", _c_p), ("out_tok", _c_p), ("out_col", _c_p), ("out_score", _c_p), ("out_dec", _c_p),
         ("out_ctc", _c_p), ("out_s", _c_p), ("nseg", _i), ("seg", _c_p),
+        ("bonus", _c_p), ("next", _c_p), ("out_bonus", _c_p), ("out_next", _c_p),
+    ]
+
+
+class HotwordParams(ctypes.Structure):
+    _fields_ = [
+        ("R", _i), ("P", _i), ("C", _i), ("nodes", _i), ("blank", _i), ("eos", _i), ("beta", _f),
+        ("child_off", _c_p), ("child_tok", _c_p), ("child_node", _c_p), ("pend", _c_p), ("terminal", _c_p),
+        ("node", _c_p), ("ids_pre", _c_p), ("ids", _c_p), ("bonus", _c_p), ("next", _c_p),
     ]
 
 
@@ -236,6 +245,7 @@ class BeamPostParams(ctypes.Structure):
         ("bp_prev", _c_p), ("bp_tok", _c_p), ("end_flag", _c_p), ("end_score", _c_p), ("end_dec", _c_p),
         ("end_ctc", _c_p), ("best_len", _c_p), ("best_end", _c_p), ("done", _c_p),
         ("upos", _c_p), ("rowpos", _c_p),
+        ("sel_bonus", _c_p), ("sel_next", _c_p), ("shw", _c_p), ("end_hw", _c_p), ("node_out", _c_p),
     ]
 
 
@@ -338,6 +348,7 @@ SYMBOLS = {
     "avsr_log_softmax_topk": ([_i, _i, _i, _c_p, _i64, _c_p, _i64, _i, _c_p, _c_p], _i),
     "avsr_ctc_prefix": ([ctypes.POINTER(CtcPrefixParams), _c_p], _i),
     "avsr_beam_select": ([ctypes.POINTER(BeamSelectParams), _c_p], _i),
+    "avsr_hotword_step": ([ctypes.POINTER(HotwordParams), _c_p], _i),
     "avsr_beam_step_prep": ([_i, _i, _c_p, _c_p, _c_p, _c_p], _i),
     "avsr_beam_kv_put": ([_i, _i, _i, _c_p, _i64, _c_p, _c_p, _c_p, _c_p], _i),
     "avsr_beam_post": ([ctypes.POINTER(BeamPostParams), _c_p], _i),

@@ -6,6 +6,8 @@
 //   avsr_ctc_prefix        CTC prefix scores of the pre-beam tokens (T recursion)
 //   avsr_beam_select       weighted scores + flat top-beam over (hyps x V)
 //   avsr_gather_rows       reorder per-hypothesis state (K/V caches, CTC variables)
+// (the hot-word bonus that avsr_beam_select / avsr_beam_post optionally carry comes from
+//  avsr_hotword_step, hotword.hip)
 // All fp32 math; decode runs at batch 1 utterance x beam hypotheses, so these kernels are
 // latency-bound: one block per row / hypothesis, no host round trip inside a step.
 #include "common.h"
@@ -586,6 +588,12 @@ __global__ __launch_bounds__(256) void ctc_prefix_lds_kernel(avsr_ctc_prefix_par
 // result when its beam-th score is above that bound for every row of the segment — then no
 // other token can enter the top beam and the result equals the full scan; otherwise (fewer
 // than `beam` finite candidates) it scans all rows x V as before.
+// With a hot-word bonus (p.bonus, added between the CTC term and score[h]) the candidates are the
+// row's P columns, continuation columns included, and eos. The candidate-only pass stays exact:
+// only a token of ids[h] can match a tree edge and earn a positive bonus; every other token takes
+// the eos column's value -beta * pend <= 0, so its score stays below the same bound, and the
+// bonus of a candidate (|b| <= beta * the deepest phrase, a few units) is far inside the 1e-3
+// relative margin under |w_ctc * LOGZERO| ~ 1e9.
 __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_params p) {
   __shared__ float shv[4];
   __shared__ int shi[4];
@@ -598,6 +606,14 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
   const int beam = min(p.beam, nrow * p.V);
   const int total = nrow * p.V;
   const int W = p.P + 1;
+  // column of token v in the hot-word bonus / next arrays of row h: its ids column, or P (the eos
+  // column) for eos and for every token outside the row's ids
+  auto bonus_col = [&](int h, int v) -> int {
+    if (v != p.eos && v != p.blank)
+      for (int c = 0; c < p.P; ++c)
+        if (p.ids[h * p.P + c] == v) return c;
+    return p.P;
+  };
   auto weighted = [&](int f) -> float {
     const int h = r0 + f / p.V, v = f - (f / p.V) * p.V;
     if (p.score[h] == -INFINITY) return -INFINITY;      // a dead row of the device-side search
@@ -609,6 +625,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
     float w = 0.f;
     w += p.w_dec * (p.dec[(int64_t)h * p.ld + v]);
     w += p.w_ctc * (psi - p.s_prev[h]);
+    if (p.bonus) w += p.bonus[h * (p.P + 1) + bonus_col(h, v)];
     w += p.score[h];
     return w;
   };
@@ -649,6 +666,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
         p.out_dec[o] = p.dec[(int64_t)h * p.ld + tok];
         p.out_ctc[o] = psi - p.s_prev[h];
         p.out_s[o] = psi;
+        if (p.bonus) {
+          const int bc = bonus_col(h, tok);
+          p.out_bonus[o] = p.bonus[h * (p.P + 1) + bc];
+          if (p.out_next) p.out_next[o] = p.next[h * (p.P + 1) + bc];
+        }
       }
     }
     return last;
@@ -666,6 +688,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
         const int o = u * p.beam + r;
         p.out_prev[o] = r0; p.out_tok[o] = p.eos; p.out_col[o] = p.P - 1; p.out_score[o] = -INFINITY;
         p.out_dec[o] = 0.f; p.out_ctc[o] = 0.f; p.out_s[o] = 0.f;
+        if (p.bonus) { p.out_bonus[o] = 0.f; if (p.out_next) p.out_next[o] = 0; }
       }
       return;
     }
@@ -676,8 +699,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
     if (c < nrow * W) {
       const int hl = c / W, k = c - hl * W, h = r0 + hl;
       const int v = k < p.P ? p.ids[h * p.P + k] : p.eos;
-      // eos once per row: as the extra candidate, not again as a pre-beam id
-      if (!(k < p.P && v == p.eos)) insert(weighted(hl * p.V + v), hl * p.V + v);
+      // eos once per row: as the extra candidate, not again as a pre-beam id. With hot words the
+      // unused continuation columns hold blank: each (row, token) must enter the lists once, and a
+      // blank is below the bound anyway
+      const bool pad = p.bonus && k < p.P && v == p.blank;
+      if (!(k < p.P && v == p.eos) && !pad) insert(weighted(hl * p.V + v), hl * p.V + v);
     }
     const float last = select();
     if (threadIdx.x == 0) {
@@ -780,9 +806,13 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
   extern __shared__ __attribute__((aligned(16))) char sm[];
   double* od = (double*)sm;                   // [R] old decoder sums
   double* oc = od + p.R;                      // [R] old CTC sums
-  int* ended = (int*)(oc + p.R);              // [R] 0 running, 1 eos, 2 forced eos at maxlen
+  double* oh = oc + p.R;                      // [R] old hot-word bonus sums (with p.sel_bonus only)
+  int* ended = (int*)(oh + (p.sel_bonus ? p.R : 0));   // [R] 0 running, 1 eos, 2 forced eos at maxlen
   const int pos0 = p.upos ? 0 : p.pos[0];
-  for (int r = threadIdx.x; r < p.R; r += 256) { od[r] = p.sdec[r]; oc[r] = p.sctc[r]; }
+  for (int r = threadIdx.x; r < p.R; r += 256) {
+    od[r] = p.sdec[r]; oc[r] = p.sctc[r];
+    if (p.sel_bonus) oh[r] = p.shw[r];
+  }
   __syncthreads();
   for (int r = threadIdx.x; r < p.R; r += 256) {
     const int u = r / p.beam;
@@ -793,6 +823,7 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
       p.score[r] = -INFINITY;
       p.src[r] = r; p.src[p.R + r] = r * p.P;
       p.bp_prev[so + r] = r; p.bp_tok[so + r] = p.eos; p.end_flag[so + r] = 0;
+      if (p.sel_bonus) p.node_out[r] = 0;
       continue;
     }
     const int h = p.sel_prev[r], t = p.sel_tok[r];
@@ -806,6 +837,12 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
     p.tok[r] = t;
     p.score[r] = e ? -INFINITY : sc;
     p.sdec[r] = nd; p.sctc[r] = nc; p.s_prev[r] = p.sel_s[r];
+    if (p.sel_bonus) {
+      const double nh = oh[h] + (double)p.sel_bonus[r];
+      if (e) p.end_hw[so + r] = nh;
+      p.shw[r] = nh;
+      p.node_out[r] = p.sel_next[r];
+    }
     p.src[r] = h; p.src[p.R + r] = h * p.P + p.sel_col[r];
   }
   __syncthreads();
@@ -925,7 +962,8 @@ extern "C" int avsr_beam_slot_reset(const avsr_beam_slot_reset_params* p, void* 
 extern "C" int avsr_beam_post(const avsr_beam_post_params* p, void* stream) {
   if (!p || p->U <= 0 || p->beam <= 0 || p->R != p->U * p->beam || p->R > 2048) return AVSR_E_ARG;
   if (p->upos ? !p->rowpos : !p->pos) return AVSR_E_ARG;
-  const size_t lds = (size_t)p->R * (2 * sizeof(double) + sizeof(int));
+  if (p->sel_bonus && (!p->sel_next || !p->shw || !p->end_hw || !p->node_out)) return AVSR_E_ARG;
+  const size_t lds = (size_t)p->R * ((p->sel_bonus ? 3 : 2) * sizeof(double) + sizeof(int));
   hipLaunchKernelGGL(beam_post_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, *p);
   AVSR_CHECK_LAUNCH();
   return 0;
@@ -983,6 +1021,7 @@ extern "C" int avsr_beam_select(const avsr_beam_select_params* p, void* stream) 
   if (p->beam < 1 || p->beam > KMAX || p->P < 1 || p->nseg < 0) return AVSR_E_SHAPE;
   if (!p->nseg && p->beam > p->n * p->V) return AVSR_E_SHAPE;
   if (p->nseg && !p->seg) return AVSR_E_ARG;
+  if (p->bonus && (!p->out_bonus || (p->out_next && !p->next))) return AVSR_E_ARG;
   hipLaunchKernelGGL(beam_select_kernel, dim3(p->nseg ? p->nseg : 1), dim3(256), 0, (hipStream_t)stream, *p);
   AVSR_CHECK_LAUNCH();
   return 0;

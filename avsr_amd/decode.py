@@ -33,6 +33,19 @@ ctc_weight = 1 on the CTC prefix scorer alone over the full vocabulary (pre_beam
 no decoder step at all): psi of every token in chunks of 64, then the row's top int(1.5*beam)
 tokens by psi (a superset of every token the flat top-beam can pick from that row, since the row
 offset is common) get their CTC states.
+
+Hot-word biasing (`set_hotwords`, avsr_amd/hotwords.py; the joint search through `bs(x)` and
+`decode_batch` only) is the one way this search takes information from outside the model: the
+reference plugs host scorers into its loop, a replayed graph has no host in its loop, so the bias
+is a kernel of the step. Every row carries a node of the phrases' prefix tree; after the pre-beam
+`ops.hotword_step` widens the row's candidates by the next tokens of a phrase it is inside (at most
+8 more columns, which get real CTC prefix scores) and gives every candidate column its bonus and
+successor node; `beam_select` adds the bonus between the CTC term and the running score, `beam_post`
+sums it in fp64 (`Hypothesis.scores["hotword"]`) and writes the selected successor into the other
+node buffer. Phrase starts are rewarded only when the decoder's pre-beam holds them. A hypothesis
+the length limit closes keeps the bonus of a phrase it had not finished: the reference appends that
+eos without scoring it, so nothing cancels there. With no phrase list none of this is allocated or
+launched.
 """
 import math
 from typing import Any, Dict, List, NamedTuple, Union
@@ -40,6 +53,7 @@ from typing import Any, Dict, List, NamedTuple, Union
 import numpy as np
 import torch
 
+from . import hotwords
 from . import ops
 from . import stream_slots
 
@@ -117,6 +131,38 @@ class BatchBeamSearch:
             raise KeyError("decoder is not a scorer (weight 0): pre_beam_score_key must be None")   # beam_search.py:92-97
         if self.use_ctc and self.use_dec and (pre_beam_score_key is None or not self.pre_beam_size < vocab_size):
             raise NotImplementedError("the joint search pre-beams on the decoder score, as the reference configures it")
+        self.hotwords, self.hotword_bonus = None, None
+        self._hotword_dev = {}
+
+    # ----------------------------------------------------------------------- hot words
+    def set_hotwords(self, phrases, bonus=None):
+        """Bias the search towards `phrases` (lists of token ids, see avsr_amd.hotwords): every
+        token that continues a phrase adds `bonus` (> 0, no default: a tuning knob nobody has
+        measured for this model) to the hypothesis score, a phrase left unfinished gives it back.
+        `set_hotwords(None)` or an empty list clears the list: the search then launches exactly what
+        it launches without this feature. The joint search only (0 < ctc_weight < 1), through
+        `bs(x)` and `decode_batch`."""
+        phrases = None if phrases is None else list(phrases)
+        if not phrases:
+            self.hotwords, self.hotword_bonus, self._hotword_dev = None, None, {}
+            return
+        if not (self.use_dec and self.use_ctc):
+            raise NotImplementedError("hot words: the joint search only (0 < ctc_weight < 1)")
+        if bonus is None or not float(bonus) > 0.0 or not math.isfinite(float(bonus)):
+            raise ValueError(f"hot words need a per-token bonus > 0 (got {bonus!r})")
+        tree = hotwords.build_tree(phrases, eos=self.eos, blank=self.blank)
+        if max(int(tree.child_tok.max()), 0) >= self.n_vocab:
+            raise ValueError(f"a phrase holds a token id outside the vocabulary of {self.n_vocab}")
+        self.hotwords, self.hotword_bonus, self._hotword_dev = tree, float(bonus), {}
+
+    def _hotword_arrays(self, dev):
+        """the tree's flat arrays on `dev` (uploaded once per device and phrase list)"""
+        key = str(dev)
+        if key not in self._hotword_dev:
+            t = self.hotwords
+            self._hotword_dev[key] = {k: torch.from_numpy(getattr(t, k)).to(dev) for k in
+                                      ("child_off", "child_tok", "child_node", "pend", "terminal")}
+        return self._hotword_dev[key]
 
     def __call__(self, x, maxlenratio: float = 0.0, minlenratio: float = 0.0):
         return self.forward(x, maxlenratio, minlenratio)
@@ -231,16 +277,28 @@ class BatchBeamSearch:
         ops.beam_step_prep(R, st["pos"], st["anc"][k], st["klen_self"], per_row="rowpos" in st)
         # decoder log-probs + the pre-beam ids; without a decoder scorer its score is 0
         dec = self._decoder_step(eng, st) if self.use_dec else st["dec0"]
+        ids, hw, sel_hw, post_hw = st["ids"], st.get("hw"), {}, {}
+        if hw is not None:
+            # hot words: the candidates widen by the continuations of each row's tree node; bonus and
+            # successor node per column (node ping-pong: read k, beam_post writes 1 - k)
+            ids = hw["ids"]
+            ops.hotword_step(hw["tree"], hw["node"][k], st["ids"], ids, hw["bonus"], hw["next"], beta=hw["beta"],
+                             blank=self.blank, eos=self.eos)
+            P = ids.shape[1]
+            sel_hw = dict(bonus=hw["bonus"], nxt=hw["next"])
         if self.use_ctc:
             r_prev = None if first else st["r_prev"][k]
             if not self.use_dec:
                 self._ctc_full_vocab(st, r_prev)
-            ops.ctc_prefix(st["logp"], r_prev, st["tok"], st["ids"], st["r_new"], st["psi"], n=R, out_len=0,
+            ops.ctc_prefix(st["logp"], r_prev, st["tok"], ids, st["r_new"], st["psi"], n=R, out_len=0,
                            out_len_dev=st["pos"], per_row="rowpos" in st, blank=self.blank, eos=self.eos,
                            uidx=st["uidx"], tlen=st["tlen"])
         out = st["out"]
-        ops.beam_select(dec, self.n_vocab, st["ids"], st["psi"], st["s_prev"], st["score"], out, n=R, beam=beam,
-                        blank=self.blank, eos=self.eos, w_dec=self.w_dec, w_ctc=self.w_ctc, seg=st["seg"])
+        ops.beam_select(dec, self.n_vocab, ids, st["psi"], st["s_prev"], st["score"], out, n=R, beam=beam,
+                        blank=self.blank, eos=self.eos, w_dec=self.w_dec, w_ctc=self.w_ctc, seg=st["seg"], **sel_hw)
+        if hw is not None:
+            post_hw = dict(sel_bonus=out["bonus"], sel_next=out["next"], shw=hw["shw"], end_hw=hw["end_hw"],
+                           node_out=hw["node"][1 - k])
         ops.beam_post(U=st["U"], beam=beam, P=P, R=R, Lmax=st["Lmax"], steps_cap=st["steps"], eos=self.eos,
                       end_detect=st["end_detect"], d_end=float(D_END), pos=st["pos"], maxlen=st["maxlen"],
                       sel_prev=out["prev"], sel_tok=out["tok"], sel_col=out["col"], sel_score=out["score"],
@@ -248,7 +306,7 @@ class BatchBeamSearch:
                       sdec=st["sdec"], sctc=st["sctc"], s_prev=st["s_prev"], src=st["src"], bp_prev=st["bp_prev"],
                       bp_tok=st["bp_tok"], end_flag=st["end_flag"], end_score=st["end_score"], end_dec=st["end_dec"],
                       end_ctc=st["end_ctc"], best_len=st["best_len"], best_end=st["best_end"], done=st["done"],
-                      upos=st.get("upos"), rowpos=st.get("rowpos"))
+                      upos=st.get("upos"), rowpos=st.get("rowpos"), **post_hw)
         Lm, Tm = st["Lmax"], st["Tm"]
         ops.gather_rows(st["anc"][k], st["anc"][1 - k], st["src"][:R], groups=1, n=R, row_bytes=Lm * 4,
                         src_gstride=0, src_rstride=Lm * 4, dst_gstride=0, dst_rstride=Lm * 4)
@@ -355,6 +413,18 @@ class BatchBeamSearch:
             end_dec=torch.zeros(steps, R, **f64), end_ctc=torch.zeros(steps, R, **f64),
             best_len=torch.full((U, Lmax + 3), float("-inf"), **f32), best_end=torch.full((U,), float("-inf"), **f32),
             done=torch.zeros(U + 1, **i32), fold=fold)
+        if self.hotwords is not None:
+            # hot words: candidates, CTC scores and states over Pw = P + C columns (st["ids"] stays
+            # the pre-beam the decoder step writes), the per-column bonus / successor node, the
+            # node of every row (root for sos; ping-pong like anc), the bonus sums and their history
+            Pw = P + hotwords.MAX_CHILDREN
+            st["psi"] = torch.empty(R, Pw + 1, **f32)
+            st["r_new"] = torch.empty(R, Pw, Tm, 2, **f32)
+            st["out"]["bonus"], st["out"]["next"] = torch.empty(R, **f32), torch.empty(R, **i32)
+            st["hw"] = dict(tree=self._hotword_arrays(dev), beta=self.hotword_bonus,
+                            ids=torch.empty(R, Pw, **i32), bonus=torch.empty(R, Pw + 1, **f32),
+                            next=torch.empty(R, Pw + 1, **i32), node=[torch.zeros(R, **i32), torch.zeros(R, **i32)],
+                            shw=torch.zeros(R, **f64), end_hw=torch.zeros(steps, R, **f64))
         if not self.use_ctc:
             st["psi"].zero_()                 # w_ctc = 0 multiplies it: keep it finite
         if not self.use_dec:
@@ -396,6 +466,7 @@ class BatchBeamSearch:
         col = slice(r0, r0 + rows)
         bp_prev, bp_tok, flag, esc, edec, ectc = (st[k][:n, col].cpu().numpy() for k in
                                                   ("bp_prev", "bp_tok", "end_flag", "end_score", "end_dec", "end_ctc"))
+        ehw = st["hw"]["end_hw"][:n, col].cpu().numpy() if "hw" in st else None
         out = []
         for i in range(n):
             for r in np.nonzero(flag[i])[0].tolist():
@@ -405,8 +476,10 @@ class BatchBeamSearch:
                     toks.append(int(bp_tok[j, h]))
                     h = int(bp_prev[j, h]) - r0
                 yseq = [self.sos] + toks[::-1] + ([self.eos] if flag[i, r] == 2 else [])
-                out.append((r, self._make_hyp(dict(yseq=yseq, score=float(esc[i, r]), dec=float(edec[i, r]),
-                                                   ctc=float(ectc[i, r])), self.use_dec, self.use_ctc)))
+                hyp = dict(yseq=yseq, score=float(esc[i, r]), dec=float(edec[i, r]), ctc=float(ectc[i, r]))
+                if ehw is not None:
+                    hyp["hotword"] = float(ehw[i, r])
+                out.append((r, self._make_hyp(hyp, self.use_dec, self.use_ctc)))
         return out
 
     def _collect(self, st, xs, maxlenratio, minlenratio):
@@ -512,12 +585,15 @@ class BatchBeamSearch:
 
     @staticmethod
     def _make_hyp(hyp, use_dec=True, use_ctc=True):
-        """the reference's Hypothesis: scores of the scorers in the search only"""
+        """the reference's Hypothesis: scores of the scorers in the search only ("hotword": the
+        summed hot-word bonus, only in a search with a phrase list)"""
         scores = {}
         if use_dec:
             scores["decoder"] = torch.tensor(hyp["dec"], dtype=torch.float32)
         if use_ctc:
             scores["ctc"] = torch.tensor(hyp["ctc"], dtype=torch.float32)
+        if "hotword" in hyp:
+            scores["hotword"] = torch.tensor(hyp["hotword"], dtype=torch.float32)
         return Hypothesis(yseq=torch.tensor(hyp["yseq"], dtype=torch.int64),
                           score=torch.tensor(hyp["score"], dtype=torch.float32), scores=scores, states={})
 
@@ -543,6 +619,8 @@ class DecodeSession:
     streams one after another; `close()` drops graphs and buffers."""
 
     def __init__(self, bs, slots=None, max_frames=375, maxlenratio=0.0, minlenratio=0.0, poll=4, graphs=True):
+        if bs.hotwords is not None:
+            raise NotImplementedError("hot words: a decode session does not carry the tree nodes; use decode_batch")
         beam = bs.beam_size
         S = stream_slots.default_slots(beam) if slots is None else int(slots)
         stream_slots.check_geometry(S, beam)
@@ -664,9 +742,12 @@ class DecodeSession:
                 yield book.finish(slot), nbest
 
 
-def get_beam_search_decoder(model, token_list, ctc_weight=0.1, beam_size=3):
-    """src/avhubert_avsr/avhubert_avsr_model.py:12-36 — `model` is the E2E (`AVHubertAVSR.avsr`)."""
+def get_beam_search_decoder(model, token_list, ctc_weight=0.1, beam_size=3, hotwords=None, hotword_bonus=None):
+    """src/avhubert_avsr/avhubert_avsr_model.py:12-36 — `model` is the E2E (`AVHubertAVSR.avsr`).
+    hotwords (token-id lists) and hotword_bonus: `set_hotwords` on the result."""
     weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": 0.0, "length_bonus": 0.0}
-    return BatchBeamSearch(model, beam_size=beam_size, vocab_size=len(token_list), weights=weights, sos=model.sos,
-                           eos=model.eos, token_list=token_list,
-                           pre_beam_score_key=None if ctc_weight == 1.0 else "decoder")
+    bs = BatchBeamSearch(model, beam_size=beam_size, vocab_size=len(token_list), weights=weights, sos=model.sos,
+                         eos=model.eos, token_list=token_list,
+                         pre_beam_score_key=None if ctc_weight == 1.0 else "decoder")
+    bs.set_hotwords(hotwords, hotword_bonus)
+    return bs

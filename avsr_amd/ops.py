@@ -1065,16 +1065,34 @@ def ctc_prefix(logp, r_prev, last, ids, r_new, psi, *, n, out_len, blank, eos, u
                                      out_len_stride=0 if out_len_dev is None else _pos_stride(out_len_dev, n, per_row)))
 
 
-def beam_select(dec, V, ids, psi, s_prev, score, out, *, n, beam, blank, eos, w_dec, w_ctc, seg=None):
+def beam_select(dec, V, ids, psi, s_prev, score, out, *, n, beam, blank, eos, w_dec, w_ctc, seg=None, bonus=None,
+                nxt=None):
     """out: dict of device tensors prev/tok/col (int32) and score/dec/ctc/s (fp32), [beam] —
     or, with seg (int32 [U+1] row offsets of U utterances), one selection per utterance into
-    out[*][u*beam + r]"""
+    out[*][u*beam + r]. bonus (n, P + 1) fp32: the hot-word bonus per ids column and for eos
+    (hotword_step), added between the CTC term and the running score; then out["bonus"] (fp32) gets
+    the selected bonus and, with nxt (n, P + 1) int32, out["next"] the selected successor node.
+    bonus None: the selection without it, and those two outputs untouched"""
+    hw = {} if bonus is None else dict(bonus=bonus, next=nxt, out_bonus=out["bonus"],
+                                       out_next=None if nxt is None else out["next"])
     _call("avsr_beam_select", L.fill(L.BeamSelectParams, n=n, V=V, P=ids.shape[1], beam=beam, blank=blank, eos=eos,
                                       w_dec=w_dec, w_ctc=w_ctc, dec=dec, ld=dec.stride(0), ids=ids, psi=psi,
                                       s_prev=s_prev, score=score, out_prev=out["prev"], out_tok=out["tok"],
                                       out_col=out["col"], out_score=out["score"], out_dec=out["dec"],
                                       out_ctc=out["ctc"], out_s=out["s"],
-                                      nseg=0 if seg is None else seg.numel() - 1, seg=seg))
+                                      nseg=0 if seg is None else seg.numel() - 1, seg=seg, **hw))
+
+
+def hotword_step(tree, node, ids_pre, ids, bonus, nxt, *, beta, blank, eos):
+    """avsr_hotword_step (avsr_hip.h): tree = dict of int32 device arrays child_off / child_tok /
+    child_node / pend / terminal (avsr_amd.hotwords.HotwordTree); node (R,), ids_pre (R, P) in;
+    ids (R, P + C), bonus / nxt (R, P + C + 1) out"""
+    R, P = ids_pre.shape
+    _call("avsr_hotword_step", L.fill(L.HotwordParams, R=R, P=P, C=ids.shape[1] - P, nodes=tree["pend"].numel(),
+                                       blank=blank, eos=eos, beta=beta, child_off=tree["child_off"],
+                                       child_tok=tree["child_tok"], child_node=tree["child_node"],
+                                       pend=tree["pend"], terminal=tree["terminal"], node=node, ids_pre=ids_pre,
+                                       ids=ids, bonus=bonus, next=nxt))
 
 
 def gather_rows(src, dst, idx, *, groups, n, row_bytes, src_gstride, src_rstride, dst_gstride, dst_rstride):

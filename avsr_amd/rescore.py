@@ -91,6 +91,12 @@ class CTCRescoringSearch:
     def __call__(self, x):
         return self.decode_batch([x])[0]
 
+    def set_hotwords(self, phrases, bonus=None):
+        """BatchBeamSearch.set_hotwords' call form: hot-word biasing lives in the joint search's
+        step, so a phrase list is refused here; None / an empty list is accepted (nothing to clear)"""
+        if phrases is not None and len(list(phrases)):
+            raise NotImplementedError("hot words: the joint search only (get_beam_search_decoder)")
+
     # ------------------------------------------------------------------- first pass
     def _ctc_logits(self, eng, xs):
         """padded memory xp (U, Tm, D) in the engine dtype and CTC logits cl (U*Tm, Vp). The CTC
@@ -252,8 +258,12 @@ class CTCRescoringSearch:
         return out
 
 
-def get_rescoring_decoder(model, token_list, ctc_weight=0.1, beam_size=10, token_beam=None):
+def get_rescoring_decoder(model, token_list, ctc_weight=0.1, beam_size=10, token_beam=None, hotwords=None,
+                          hotword_bonus=None):
     """the two-pass counterpart of get_beam_search_decoder — `model` is the E2E
-    (`AVHubertAVSR.avsr`); the result has the same call forms (bs(x), decode_batch(xs))"""
-    return CTCRescoringSearch(model, beam_size=beam_size, token_beam=token_beam, ctc_weight=ctc_weight, sos=model.sos,
-                              eos=model.eos, token_list=token_list)
+    (`AVHubertAVSR.avsr`); the result has the same call forms (bs(x), decode_batch(xs)). A hot-word
+    list is refused (NotImplementedError): biasing is part of the joint search only"""
+    search = CTCRescoringSearch(model, beam_size=beam_size, token_beam=token_beam, ctc_weight=ctc_weight,
+                                sos=model.sos, eos=model.eos, token_list=token_list)
+    search.set_hotwords(hotwords, hotword_bonus)
+    return search

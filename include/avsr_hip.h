@@ -836,8 +836,52 @@ typedef struct {
   /* batched utterances (nseg 0: one selection over all n rows): selection u runs over rows
    * [seg[u], seg[u+1]) and writes out_*[u*beam + r]; out_prev is the global row index */
   int nseg; const int* seg;
+  /* hot-word biasing (NULL: off, the selection above unchanged). bonus / next [n][P+1] as
+   * avsr_hotword_step writes them for this launch's ids (P counts its continuation columns):
+   * weighted[h][v] = w_dec*dec + w_ctc*(psi - s_prev) + bonus[h][c] + score[h], the four terms
+   * added in this order, c = the column of v in ids[h], or P for eos and for every token outside
+   * ids[h] (such a token leaves a started phrase like eos does). out_bonus = the selected bonus,
+   * out_next = next[h][c]; both set together with bonus (next may be NULL with out_next). */
+  const float* bonus; const int* next;
+  float* out_bonus; int* out_next;
 } avsr_beam_select_params;
 int avsr_beam_select(const avsr_beam_select_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Hot-word biasing of the beam search (avsr_amd/hotwords.py builds the tree; the reference has
+ * no counterpart: its scorers are host objects, src/nets/scorer_interface.py). A prefix tree over
+ * the user's phrases in CSR form: the children of node n are entries [child_off[n],
+ * child_off[n+1]) of child_tok (ascending) / child_node; node 0 is the root; pend[n] = depth(n)
+ * minus the depth of the nearest terminal ancestor-or-self (0 without one); terminal[n] = a phrase
+ * ends at n. Row r of the search stands at node[r] (the root for sos).
+ * avsr_hotword_step, once per step after the pre-beam: the row's candidate ids
+ *   ids[r][0..P) = ids_pre[r][:], ids[r][P + j] = the j-th child token of node[r] for a non-root
+ *   node (j < C = AVSR_HOTWORD_C), or blank when there is none or the pre-beam already holds it
+ *   (no candidate twice); and for every column c < P + C and the eos column c = P + C:
+ *   bonus[r][c] = beta * (float)k and next[r][c], where for the column's token v
+ *     child(node, v) = m exists:  k = 1, next = m, or the root if m is terminal without children
+ *     v is eos or blank:          k = -pend[node], next = root
+ *     otherwise:                  k = -pend[node]; then child(root, v) = m exists: k += 1 and
+ *                                 next = m (same terminal rule), else next = root
+ *   A node outside [0, nodes) is read as the root. The CTC prefix scores, the selection and the
+ *   bookkeeping then run over P + C columns. */
+enum { AVSR_HOTWORD_C = 8 };
+typedef struct {
+  int R, P, C, nodes;
+  int blank, eos;
+  float beta;
+  const int* child_off;       /* [nodes + 1] */
+  const int* child_tok;       /* [nodes - 1] */
+  const int* child_node;      /* [nodes - 1] */
+  const int* pend;            /* [nodes] */
+  const int* terminal;        /* [nodes] */
+  const int* node;            /* [R] */
+  const int* ids_pre;         /* [R][P] */
+  int* ids;                   /* [R][P + C] */
+  float* bonus;               /* [R][P + C + 1] */
+  int* next;                  /* [R][P + C + 1] */
+} avsr_hotword_params;
+int avsr_hotword_step(const avsr_hotword_params* p, void* stream);
 
 int avsr_gather_rows(int groups, int n, int64_t row_bytes, const void* src, int64_t src_gstride,
                      int64_t src_rstride, void* dst, int64_t dst_gstride, int64_t dst_rstride,
@@ -885,6 +929,13 @@ typedef struct {
   int* done;                 /* [U + 1]: per utterance, then the count */
   int* upos;                 /* [U] or NULL: per-slot positions (see above) */
   int* rowpos;               /* [R], with upos */
+  /* hot-word biasing (sel_bonus NULL: off): the selected bonus is summed per hypothesis in double
+   * like sdec / sctc (shw[R]) and recorded with an ended hypothesis (end_hw, same shape as
+   * end_dec); node_out[r] = sel_next[r], the root for a row of a finished utterance: the other
+   * buffer of the node ping-pong, which the next step's avsr_hotword_step reads. A hypothesis
+   * ended by the step limit keeps the bonus of an unfinished phrase (its eos is not scored). */
+  const float* sel_bonus; const int* sel_next;
+  double* shw; double* end_hw; int* node_out;
 } avsr_beam_post_params;
 typedef struct {
   int U, beam, R, Lmax, slot, sos;
