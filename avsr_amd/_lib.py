@@ -224,6 +224,29 @@ class BeamSelectParams(ctypes.Structure):
         ("out_prev", _c_p), ("out_tok", _c_p), ("out_col", _c_p), ("out_score", _c_p), ("out_dec", _c_p),
         ("out_ctc", _c_p), ("out_s", _c_p), ("nseg", _i), ("seg", _c_p),
         ("bonus", _c_p), ("next", _c_p), ("out_bonus", _c_p), ("out_next", _c_p),
+        ("lm", _c_p), ("lm_next", _c_p), ("w_lm", _f), ("w_len", _f), ("lm_hi", _f), ("out_lm", _c_p),
+        ("out_lm_next", _c_p),
+    ]
+
+
+class NgramLMStruct(ctypes.Structure):
+    _fields_ = [
+        ("order", _i), ("nodes", _i), ("V", _i), ("start", _i),
+        ("child_off", _c_p), ("backoff", _c_p), ("fail", _c_p), ("tok", _c_p), ("logp", _c_p), ("next", _c_p),
+        ("uni_logp", _c_p), ("uni_next", _c_p),
+    ]
+
+
+class NgramParams(ctypes.Structure):
+    _fields_ = [
+        ("lm", NgramLMStruct), ("R", _i), ("P", _i), ("blank", _i), ("eos", _i),
+        ("state", _c_p), ("ids", _c_p), ("out", _c_p), ("out_next", _c_p),
+    ]
+
+
+class NgramSeqParams(ctypes.Structure):
+    _fields_ = [
+        ("lm", NgramLMStruct), ("n", _i), ("L", _i), ("eos", _i), ("tokens", _c_p), ("out", _c_p),
     ]
 
 
@@ -246,6 +269,8 @@ class BeamPostParams(ctypes.Structure):
         ("end_ctc", _c_p), ("best_len", _c_p), ("best_end", _c_p), ("done", _c_p),
         ("upos", _c_p), ("rowpos", _c_p),
         ("sel_bonus", _c_p), ("sel_next", _c_p), ("shw", _c_p), ("end_hw", _c_p), ("node_out", _c_p),
+        ("sel_lm", _c_p), ("sel_lm_next", _c_p), ("slm", _c_p), ("end_lm", _c_p), ("lm_state_out", _c_p),
+        ("slen", _c_p), ("end_len", _c_p), ("lm_start", _i),
     ]
 
 
@@ -349,6 +374,8 @@ SYMBOLS = {
     "avsr_ctc_prefix": ([ctypes.POINTER(CtcPrefixParams), _c_p], _i),
     "avsr_beam_select": ([ctypes.POINTER(BeamSelectParams), _c_p], _i),
     "avsr_hotword_step": ([ctypes.POINTER(HotwordParams), _c_p], _i),
+    "avsr_ngram_step": ([ctypes.POINTER(NgramParams), _c_p], _i),
+    "avsr_ngram_score_seqs": ([ctypes.POINTER(NgramSeqParams), _c_p], _i),
     "avsr_beam_step_prep": ([_i, _i, _c_p, _c_p, _c_p, _c_p], _i),
     "avsr_beam_kv_put": ([_i, _i, _i, _c_p, _i64, _c_p, _c_p, _c_p, _c_p], _i),
     "avsr_beam_post": ([ctypes.POINTER(BeamPostParams), _c_p], _i),

@@ -7,7 +7,7 @@
 //   avsr_beam_select       weighted scores + flat top-beam over (hyps x V)
 //   avsr_gather_rows       reorder per-hypothesis state (K/V caches, CTC variables)
 // (the hot-word bonus that avsr_beam_select / avsr_beam_post optionally carry comes from
-//  avsr_hotword_step, hotword.hip)
+//  avsr_hotword_step, hotword.hip; the n-gram LM scores from avsr_ngram_step, ngram.hip)
 // All fp32 math; decode runs at batch 1 utterance x beam hypotheses, so these kernels are
 // latency-bound: one block per row / hypothesis, no host round trip inside a step.
 #include "common.h"
@@ -594,6 +594,14 @@ __global__ __launch_bounds__(256) void ctc_prefix_lds_kernel(avsr_ctc_prefix_par
 // the eos column's value -beta * pend <= 0, so its score stays below the same bound, and the
 // bonus of a candidate (|b| <= beta * the deepest phrase, a few units) is far inside the 1e-3
 // relative margin under |w_ctc * LOGZERO| ~ 1e9.
+// With an n-gram LM / a length bonus (p.lm, p.w_len; scores from avsr_ngram_step, ngram.hip) the
+// sum takes the reference's order: w_dec*dec + w_len + w_lm*lm + w_ctc*(psi - s_prev) [+ bonus] +
+// score[h]. A token outside a row's candidates takes an LM term of 0: it sits at w_ctc * LOGZERO ~
+// -1e9 * w_ctc, where one fp32 step (>= 64 * w_ctc) exceeds any LM score, so the term would round
+// away had it been computed. The candidates-only pass stays exact: a non-candidate's score is at
+// most w_len + w_lm * lm_hi + w_ctc * (LOGZERO - s_prev[h]) + score[h] (dec <= 0, its LM term 0 <=
+// w_lm * max(0, any score) <= w_lm * lm_hi, a bonus <= 0 as above), which is the bound the pass
+// compares its beam-th score with; with both off (lm NULL, w_len 0) the expressions of before run.
 __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_params p) {
   __shared__ float shv[4];
   __shared__ int shi[4];
@@ -614,6 +622,16 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
         if (p.ids[h * p.P + c] == v) return c;
     return p.P;
   };
+  // column of token v in the LM score / successor arrays of row h: its ids column, P for eos, -1
+  // for a token outside the row's candidates (LM term 0)
+  auto lm_col = [&](int h, int v) -> int {
+    if (v == p.eos) return p.P;
+    if (v != p.blank)
+      for (int c = 0; c < p.P; ++c)
+        if (p.ids[h * p.P + c] == v) return c;
+    return -1;
+  };
+  const bool fused = p.lm || p.w_len != 0.f;            // shallow fusion: the reference's summation order
   auto weighted = [&](int f) -> float {
     const int h = r0 + f / p.V, v = f - (f / p.V) * p.V;
     if (p.score[h] == -INFINITY) return -INFINITY;      // a dead row of the device-side search
@@ -624,6 +642,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
         if (p.ids[h * p.P + c] == v) { psi = p.psi[h * (p.P + 1) + c]; break; }
     float w = 0.f;
     w += p.w_dec * (p.dec[(int64_t)h * p.ld + v]);
+    if (fused) {
+      w += p.w_len;
+      if (p.lm) {
+        const int lc = lm_col(h, v);
+        w += p.w_lm * (lc >= 0 ? p.lm[h * (p.P + 1) + lc] : 0.f);
+      }
+    }
     w += p.w_ctc * (psi - p.s_prev[h]);
     if (p.bonus) w += p.bonus[h * (p.P + 1) + bonus_col(h, v)];
     w += p.score[h];
@@ -671,6 +696,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
           p.out_bonus[o] = p.bonus[h * (p.P + 1) + bc];
           if (p.out_next) p.out_next[o] = p.next[h * (p.P + 1) + bc];
         }
+        if (p.lm) {
+          const int lc = lm_col(h, tok);
+          p.out_lm[o] = lc >= 0 ? p.lm[h * (p.P + 1) + lc] : 0.f;
+          p.out_lm_next[o] = lc >= 0 ? p.lm_next[h * (p.P + 1) + lc] : -1;
+        }
       }
     }
     return last;
@@ -689,6 +719,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
         p.out_prev[o] = r0; p.out_tok[o] = p.eos; p.out_col[o] = p.P - 1; p.out_score[o] = -INFINITY;
         p.out_dec[o] = 0.f; p.out_ctc[o] = 0.f; p.out_s[o] = 0.f;
         if (p.bonus) { p.out_bonus[o] = 0.f; if (p.out_next) p.out_next[o] = 0; }
+        if (p.lm) { p.out_lm[o] = 0.f; p.out_lm_next[o] = -1; }
       }
       return;
     }
@@ -702,7 +733,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
       // eos once per row: as the extra candidate, not again as a pre-beam id. With hot words the
       // unused continuation columns hold blank: each (row, token) must enter the lists once, and a
       // blank is below the bound anyway
-      const bool pad = p.bonus && k < p.P && v == p.blank;
+      const bool pad = (p.bonus || p.lm) && k < p.P && v == p.blank;
       if (!(k < p.P && v == p.eos) && !pad) insert(weighted(hl * p.V + v), hl * p.V + v);
     }
     const float last = select();
@@ -711,7 +742,9 @@ __global__ __launch_bounds__(256) void beam_select_kernel(avsr_beam_select_param
       float bound = -INFINITY;
       for (int hl = 0; hl < nrow; ++hl) {
         const int h = r0 + hl;
-        bound = fmaxf(bound, p.w_ctc * (LOGZERO - p.s_prev[h]) + p.score[h]);
+        float b = p.w_ctc * (LOGZERO - p.s_prev[h]) + p.score[h];
+        if (fused) b += p.w_len + (p.lm ? p.w_lm * p.lm_hi : 0.f);
+        bound = fmaxf(bound, b);
       }
       use_full = !(last > bound + 1e-3f * fabsf(bound));
     }
@@ -807,11 +840,15 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
   double* od = (double*)sm;                   // [R] old decoder sums
   double* oc = od + p.R;                      // [R] old CTC sums
   double* oh = oc + p.R;                      // [R] old hot-word bonus sums (with p.sel_bonus only)
-  int* ended = (int*)(oh + (p.sel_bonus ? p.R : 0));   // [R] 0 running, 1 eos, 2 forced eos at maxlen
+  double* ol = oh + (p.sel_bonus ? p.R : 0);  // [R] old LM sums (with p.sel_lm only)
+  double* on = ol + (p.sel_lm ? p.R : 0);     // [R] old scored-token counts (with p.slen only)
+  int* ended = (int*)(on + (p.slen ? p.R : 0));        // [R] 0 running, 1 eos, 2 forced eos at maxlen
   const int pos0 = p.upos ? 0 : p.pos[0];
   for (int r = threadIdx.x; r < p.R; r += 256) {
     od[r] = p.sdec[r]; oc[r] = p.sctc[r];
     if (p.sel_bonus) oh[r] = p.shw[r];
+    if (p.sel_lm) ol[r] = p.slm[r];
+    if (p.slen) on[r] = p.slen[r];
   }
   __syncthreads();
   for (int r = threadIdx.x; r < p.R; r += 256) {
@@ -824,6 +861,7 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
       p.src[r] = r; p.src[p.R + r] = r * p.P;
       p.bp_prev[so + r] = r; p.bp_tok[so + r] = p.eos; p.end_flag[so + r] = 0;
       if (p.sel_bonus) p.node_out[r] = 0;
+      if (p.sel_lm) p.lm_state_out[r] = p.lm_start;
       continue;
     }
     const int h = p.sel_prev[r], t = p.sel_tok[r];
@@ -842,6 +880,17 @@ __global__ __launch_bounds__(256) void beam_post_kernel(avsr_beam_post_params p)
       if (e) p.end_hw[so + r] = nh;
       p.shw[r] = nh;
       p.node_out[r] = p.sel_next[r];
+    }
+    if (p.sel_lm) {
+      const double nl = ol[h] + (double)p.sel_lm[r];
+      if (e) p.end_lm[so + r] = nl;
+      p.slm[r] = nl;
+      p.lm_state_out[r] = p.sel_lm_next[r];
+    }
+    if (p.slen) {                              // the forced eos is appended unscored: one token per step
+      const double nn = on[h] + 1.0;
+      if (e) p.end_len[so + r] = nn;
+      p.slen[r] = nn;
     }
     p.src[r] = h; p.src[p.R + r] = h * p.P + p.sel_col[r];
   }
@@ -963,7 +1012,11 @@ extern "C" int avsr_beam_post(const avsr_beam_post_params* p, void* stream) {
   if (!p || p->U <= 0 || p->beam <= 0 || p->R != p->U * p->beam || p->R > 2048) return AVSR_E_ARG;
   if (p->upos ? !p->rowpos : !p->pos) return AVSR_E_ARG;
   if (p->sel_bonus && (!p->sel_next || !p->shw || !p->end_hw || !p->node_out)) return AVSR_E_ARG;
-  const size_t lds = (size_t)p->R * ((p->sel_bonus ? 3 : 2) * sizeof(double) + sizeof(int));
+  if (p->sel_lm && (!p->sel_lm_next || !p->slm || !p->end_lm || !p->lm_state_out)) return AVSR_E_ARG;
+  if (p->slen && !p->end_len) return AVSR_E_ARG;
+  const int sums = 2 + (p->sel_bonus ? 1 : 0) + (p->sel_lm ? 1 : 0) + (p->slen ? 1 : 0);
+  const size_t lds = (size_t)p->R * (sums * sizeof(double) + sizeof(int));
+  if (lds > 64 * 1024) return AVSR_E_SHAPE;
   hipLaunchKernelGGL(beam_post_kernel, dim3(1), dim3(256), lds, (hipStream_t)stream, *p);
   AVSR_CHECK_LAUNCH();
   return 0;
@@ -1022,6 +1075,8 @@ extern "C" int avsr_beam_select(const avsr_beam_select_params* p, void* stream) 
   if (!p->nseg && p->beam > p->n * p->V) return AVSR_E_SHAPE;
   if (p->nseg && !p->seg) return AVSR_E_ARG;
   if (p->bonus && (!p->out_bonus || (p->out_next && !p->next))) return AVSR_E_ARG;
+  if (p->lm && (!p->lm_next || !p->out_lm || !p->out_lm_next)) return AVSR_E_ARG;
+  if (!(p->w_lm >= 0.f) || !(p->w_len == p->w_len)) return AVSR_E_ARG;
   hipLaunchKernelGGL(beam_select_kernel, dim3(p->nseg ? p->nseg : 1), dim3(256), 0, (hipStream_t)stream, *p);
   AVSR_CHECK_LAUNCH();
   return 0;

@@ -46,6 +46,16 @@ node buffer. Phrase starts are rewarded only when the decoder's pre-beam holds t
 the length limit closes keeps the bonus of a phrase it had not finished: the reference appends that
 eos without scoring it, so nothing cancels there. With no phrase list none of this is allocated or
 launched.
+
+Shallow fusion with a token-level n-gram LM and the length bonus (`set_lm`, avsr_amd/ngram_lm.py;
+the "lm" and "length_bonus" slots of the reference's scorer dict, which it hard-wires off) follow
+the same route: every row carries a state of the LM's backoff automaton, `ops.ngram_step` scores
+the row's (widened) candidate columns and eos after the pre-beam, `beam_select` adds
+w_len + w_lm * lm in the reference's summation order (full scorers, then partial scorers, then the
+running score), `beam_post` sums both in fp64 (`Hypothesis.scores["lm"]`, the unweighted sum, and
+`scores["length_bonus"]`, the number of scored tokens) and writes the successor state into the other
+state buffer. Same scope as hot words: the joint search through `bs(x)` and `decode_batch`; with
+neither set nothing of it is allocated or launched.
 """
 import math
 from typing import Any, Dict, List, NamedTuple, Union
@@ -54,6 +64,7 @@ import numpy as np
 import torch
 
 from . import hotwords
+from . import ngram_lm
 from . import ops
 from . import stream_slots
 
@@ -133,6 +144,8 @@ class BatchBeamSearch:
             raise NotImplementedError("the joint search pre-beams on the decoder score, as the reference configures it")
         self.hotwords, self.hotword_bonus = None, None
         self._hotword_dev = {}
+        self.lm, self.w_lm, self.w_len = None, 0.0, 0.0
+        self._lm_dev = ngram_lm.FusionArrays()
 
     # ----------------------------------------------------------------------- hot words
     def set_hotwords(self, phrases, bonus=None):
@@ -163,6 +176,23 @@ class BatchBeamSearch:
             self._hotword_dev[key] = {k: torch.from_numpy(getattr(t, k)).to(dev) for k in
                                       ("child_off", "child_tok", "child_node", "pend", "terminal")}
         return self._hotword_dev[key]
+
+    # ----------------------------------------------------------------------- LM shallow fusion
+    def set_lm(self, lm, weight=0.0, length_bonus=0.0):
+        """Shallow fusion with `lm` (an avsr_amd.ngram_lm.NgramLM over this search's token ids) at
+        weight `weight` (finite, >= 0), and `length_bonus` (finite) added per scored token, which may
+        be set alone: score = (1-w)*dec + w*ctc + weight*lm + length_bonus*len [+ hotword]. Good
+        values of either are unmeasured for this model. `set_lm(None, 0.0)` clears both: the search
+        then launches exactly what it launches without this feature. The joint search only
+        (0 < ctc_weight < 1), through `bs(x)` and `decode_batch`."""
+        lm, weight, length_bonus = ngram_lm.check_fusion(lm, weight, length_bonus, self.n_vocab, self.sos, self.eos)
+        if (lm is not None or length_bonus != 0.0) and not (self.use_dec and self.use_ctc):
+            raise NotImplementedError(
+                "LM fusion / length bonus: the joint search only (0 < ctc_weight < 1); at ctc_weight 0 or 1 every "
+                "vocabulary entry is a candidate, which would need a V-wide LM pass. Use a ctc_weight inside (0, 1), "
+                "or the two-pass decoder (get_rescoring_decoder), which takes an LM at every ctc_weight")
+        self.lm, self.w_lm, self.w_len = lm, weight, length_bonus
+        self.weights = {**self.weights, "lm": self.w_lm, "length_bonus": self.w_len}
 
     def __call__(self, x, maxlenratio: float = 0.0, minlenratio: float = 0.0):
         return self.forward(x, maxlenratio, minlenratio)
@@ -286,6 +316,14 @@ class BatchBeamSearch:
                              blank=self.blank, eos=self.eos)
             P = ids.shape[1]
             sel_hw = dict(bonus=hw["bonus"], nxt=hw["next"])
+        lm = st.get("lm")
+        if lm is not None and "arrays" in lm:
+            # the LM scores the widened ids (continuation columns too) and eos from each row's state
+            # (state ping-pong: read k, beam_post writes 1 - k)
+            ops.ngram_step(lm["arrays"], lm["state"][k], ids, lm["score"], lm["next"], blank=self.blank, eos=self.eos)
+            sel_hw.update(lm=lm["score"], lm_next=lm["next"], w_lm=self.w_lm, lm_hi=lm["arrays"]["lm_hi"])
+        if lm is not None:
+            sel_hw["w_len"] = self.w_len
         if self.use_ctc:
             r_prev = None if first else st["r_prev"][k]
             if not self.use_dec:
@@ -299,6 +337,11 @@ class BatchBeamSearch:
         if hw is not None:
             post_hw = dict(sel_bonus=out["bonus"], sel_next=out["next"], shw=hw["shw"], end_hw=hw["end_hw"],
                            node_out=hw["node"][1 - k])
+        if lm is not None and "arrays" in lm:
+            post_hw.update(sel_lm=out["lm"], sel_lm_next=out["lm_next"], slm=lm["slm"], end_lm=lm["end_lm"],
+                           lm_state_out=lm["state"][1 - k], lm_start=lm["arrays"]["start"])
+        if lm is not None and "slen" in lm:
+            post_hw.update(slen=lm["slen"], end_len=lm["end_len"])
         ops.beam_post(U=st["U"], beam=beam, P=P, R=R, Lmax=st["Lmax"], steps_cap=st["steps"], eos=self.eos,
                       end_detect=st["end_detect"], d_end=float(D_END), pos=st["pos"], maxlen=st["maxlen"],
                       sel_prev=out["prev"], sel_tok=out["tok"], sel_col=out["col"], sel_score=out["score"],
@@ -425,6 +468,20 @@ class BatchBeamSearch:
                             ids=torch.empty(R, Pw, **i32), bonus=torch.empty(R, Pw + 1, **f32),
                             next=torch.empty(R, Pw + 1, **i32), node=[torch.zeros(R, **i32), torch.zeros(R, **i32)],
                             shw=torch.zeros(R, **f64), end_hw=torch.zeros(steps, R, **f64))
+        if self.lm is not None or self.w_len != 0.0:
+            # LM fusion / length bonus: the LM state of every row (<s> for sos; ping-pong like anc), the
+            # per-column score / successor over the (widened) candidate columns, the fp64 sums and
+            # their history; each only for a scorer of non-zero weight
+            lm = st["lm"] = {}
+            if self.lm is not None:
+                arr = self._lm_dev.get(self.lm, dev)
+                Wc = st["psi"].shape[1]
+                st["out"]["lm"], st["out"]["lm_next"] = torch.empty(R, **f32), torch.empty(R, **i32)
+                lm.update(arrays=arr, state=[torch.full((R,), arr["start"], **i32) for _ in range(2)],
+                          score=torch.empty(R, Wc, **f32), next=torch.empty(R, Wc, **i32),
+                          slm=torch.zeros(R, **f64), end_lm=torch.zeros(steps, R, **f64))
+            if self.w_len != 0.0:
+                lm.update(slen=torch.zeros(R, **f64), end_len=torch.zeros(steps, R, **f64))
         if not self.use_ctc:
             st["psi"].zero_()                 # w_ctc = 0 multiplies it: keep it finite
         if not self.use_dec:
@@ -467,6 +524,8 @@ class BatchBeamSearch:
         bp_prev, bp_tok, flag, esc, edec, ectc = (st[k][:n, col].cpu().numpy() for k in
                                                   ("bp_prev", "bp_tok", "end_flag", "end_score", "end_dec", "end_ctc"))
         ehw = st["hw"]["end_hw"][:n, col].cpu().numpy() if "hw" in st else None
+        extra = {name: st["lm"][k][:n, col].cpu().numpy() for name, k in (("lm", "end_lm"), ("length_bonus", "end_len"))
+                 if k in st.get("lm", {})}
         out = []
         for i in range(n):
             for r in np.nonzero(flag[i])[0].tolist():
@@ -479,6 +538,8 @@ class BatchBeamSearch:
                 hyp = dict(yseq=yseq, score=float(esc[i, r]), dec=float(edec[i, r]), ctc=float(ectc[i, r]))
                 if ehw is not None:
                     hyp["hotword"] = float(ehw[i, r])
+                for name, a in extra.items():
+                    hyp[name] = float(a[i, r])
                 out.append((r, self._make_hyp(hyp, self.use_dec, self.use_ctc)))
         return out
 
@@ -586,14 +647,16 @@ class BatchBeamSearch:
     @staticmethod
     def _make_hyp(hyp, use_dec=True, use_ctc=True):
         """the reference's Hypothesis: scores of the scorers in the search only ("hotword": the
-        summed hot-word bonus, only in a search with a phrase list)"""
+        summed hot-word bonus, only in a search with a phrase list; "lm": the unweighted LM sum and
+        "length_bonus": the number of scored tokens, each only at a non-zero weight)"""
         scores = {}
         if use_dec:
             scores["decoder"] = torch.tensor(hyp["dec"], dtype=torch.float32)
         if use_ctc:
             scores["ctc"] = torch.tensor(hyp["ctc"], dtype=torch.float32)
-        if "hotword" in hyp:
-            scores["hotword"] = torch.tensor(hyp["hotword"], dtype=torch.float32)
+        for k in ("hotword", "length_bonus", "lm"):
+            if k in hyp:
+                scores[k] = torch.tensor(hyp[k], dtype=torch.float32)
         return Hypothesis(yseq=torch.tensor(hyp["yseq"], dtype=torch.int64),
                           score=torch.tensor(hyp["score"], dtype=torch.float32), scores=scores, states={})
 
@@ -621,6 +684,9 @@ class DecodeSession:
     def __init__(self, bs, slots=None, max_frames=375, maxlenratio=0.0, minlenratio=0.0, poll=4, graphs=True):
         if bs.hotwords is not None:
             raise NotImplementedError("hot words: a decode session does not carry the tree nodes; use decode_batch")
+        if bs.lm is not None or bs.w_len != 0.0:
+            raise NotImplementedError("LM fusion / length bonus: a decode session does not reset the LM state of a "
+                                      "refilled slot; use decode_batch")
         beam = bs.beam_size
         S = stream_slots.default_slots(beam) if slots is None else int(slots)
         stream_slots.check_geometry(S, beam)
@@ -742,12 +808,15 @@ class DecodeSession:
                 yield book.finish(slot), nbest
 
 
-def get_beam_search_decoder(model, token_list, ctc_weight=0.1, beam_size=3, hotwords=None, hotword_bonus=None):
+def get_beam_search_decoder(model, token_list, ctc_weight=0.1, beam_size=3, hotwords=None, hotword_bonus=None,
+                            lm=None, lm_weight=0.0, length_bonus=0.0):
     """src/avhubert_avsr/avhubert_avsr_model.py:12-36 — `model` is the E2E (`AVHubertAVSR.avsr`).
-    hotwords (token-id lists) and hotword_bonus: `set_hotwords` on the result."""
+    hotwords (token-id lists) and hotword_bonus: `set_hotwords` on the result; lm (an NgramLM),
+    lm_weight and length_bonus: `set_lm` (the two scorer slots the reference hard-wires to 0)."""
     weights = {"decoder": 1.0 - ctc_weight, "ctc": ctc_weight, "lm": 0.0, "length_bonus": 0.0}
     bs = BatchBeamSearch(model, beam_size=beam_size, vocab_size=len(token_list), weights=weights, sos=model.sos,
                          eos=model.eos, token_list=token_list,
                          pre_beam_score_key=None if ctc_weight == 1.0 else "decoder")
     bs.set_hotwords(hotwords, hotword_bonus)
+    bs.set_lm(lm, lm_weight, length_bonus)
     return bs

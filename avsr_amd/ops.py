@@ -1066,15 +1066,22 @@ def ctc_prefix(logp, r_prev, last, ids, r_new, psi, *, n, out_len, blank, eos, u
 
 
 def beam_select(dec, V, ids, psi, s_prev, score, out, *, n, beam, blank, eos, w_dec, w_ctc, seg=None, bonus=None,
-                nxt=None):
+                nxt=None, lm=None, lm_next=None, w_lm=0.0, w_len=0.0, lm_hi=0.0):
     """out: dict of device tensors prev/tok/col (int32) and score/dec/ctc/s (fp32), [beam] —
     or, with seg (int32 [U+1] row offsets of U utterances), one selection per utterance into
     out[*][u*beam + r]. bonus (n, P + 1) fp32: the hot-word bonus per ids column and for eos
     (hotword_step), added between the CTC term and the running score; then out["bonus"] (fp32) gets
     the selected bonus and, with nxt (n, P + 1) int32, out["next"] the selected successor node.
-    bonus None: the selection without it, and those two outputs untouched"""
+    bonus None: the selection without it, and those two outputs untouched. lm / lm_next (n, P + 1)
+    fp32 / int32 (ngram_step) with the weight w_lm and the bound lm_hi, and the length bonus w_len:
+    the sum in the reference's order (avsr_hip.h); with lm, out["lm"] (fp32, unweighted) and
+    out["lm_next"] (int32) get the selected column's. lm None and w_len 0: the selection of before"""
     hw = {} if bonus is None else dict(bonus=bonus, next=nxt, out_bonus=out["bonus"],
                                        out_next=None if nxt is None else out["next"])
+    if lm is not None:
+        hw.update(lm=lm, lm_next=lm_next, w_lm=w_lm, lm_hi=lm_hi, out_lm=out["lm"], out_lm_next=out["lm_next"])
+    if w_len:
+        hw["w_len"] = w_len
     _call("avsr_beam_select", L.fill(L.BeamSelectParams, n=n, V=V, P=ids.shape[1], beam=beam, blank=blank, eos=eos,
                                       w_dec=w_dec, w_ctc=w_ctc, dec=dec, ld=dec.stride(0), ids=ids, psi=psi,
                                       s_prev=s_prev, score=score, out_prev=out["prev"], out_tok=out["tok"],
@@ -1093,6 +1100,43 @@ def hotword_step(tree, node, ids_pre, ids, bonus, nxt, *, beta, blank, eos):
                                        child_tok=tree["child_tok"], child_node=tree["child_node"],
                                        pend=tree["pend"], terminal=tree["terminal"], node=node, ids_pre=ids_pre,
                                        ids=ids, bonus=bonus, next=nxt))
+
+
+def _ngram_struct(lm):
+    """avsr_ngram_lm from lm = dict of the device arrays of an avsr_amd.ngram_lm.NgramLM (child_off,
+    backoff, fail, tok, logp, next, uni_logp, uni_next) and its ints order / nodes / V / start"""
+    return L.fill(L.NgramLMStruct, order=lm["order"], nodes=lm["nodes"], V=lm["V"], start=lm["start"],
+                  child_off=lm["child_off"], backoff=lm["backoff"], fail=lm["fail"],
+                  tok=lm["tok"] if lm["tok"].numel() else None, logp=lm["logp"] if lm["logp"].numel() else None,
+                  next=lm["next"] if lm["next"].numel() else None, uni_logp=lm["uni_logp"], uni_next=lm["uni_next"])
+
+
+def ngram_arrays(lm, device):
+    """the device form of an NgramLM that ngram_step / ngram_score_seqs take"""
+    d = {k: torch.from_numpy(getattr(lm, k)).to(device) for k in lm.ARRAYS}
+    d.update(order=lm.order, nodes=lm.nodes, V=lm.n_vocab, start=lm.start, lm_hi=lm.lm_hi)
+    return d
+
+
+def ngram_step(lm, state, ids, out, out_next, *, blank, eos):
+    """avsr_ngram_step (avsr_hip.h): lm = ngram_arrays(...); state (R,) int32, ids (R, P) int32 in;
+    out (R, P + 1) fp32 token scores and out_next (R, P + 1) int32 successor states out"""
+    R, P = ids.shape
+    _call("avsr_ngram_step", L.fill(L.NgramParams, lm=_ngram_struct(lm), R=R, P=P, blank=blank, eos=eos, state=state,
+                                     ids=ids, out=out, out_next=out_next))
+
+
+def ngram_score_seqs(lm, tokens, *, eos, out=None):
+    """avsr_ngram_score_seqs (avsr_hip.h): tokens (n, L) int32, -1 padded -> out (n, L + 1) fp32, the
+    LM score of every token and of the closing eos from the <s> state, 0 beyond"""
+    n, Lt = tokens.shape
+    if tokens.dtype != torch.int32 or not tokens.is_contiguous():
+        raise TypeError("ngram_score_seqs: tokens int32, contiguous")
+    if out is None:
+        out = torch.empty(n, Lt + 1, device=tokens.device, dtype=torch.float32)
+    _call("avsr_ngram_score_seqs", L.fill(L.NgramSeqParams, lm=_ngram_struct(lm), n=n, L=Lt, eos=eos,
+                                           tokens=tokens if Lt else None, out=out))
+    return out
 
 
 def gather_rows(src, dst, idx, *, groups, n, row_bytes, src_gstride, src_rstride, dst_gstride, dst_rstride):

@@ -29,12 +29,19 @@ score, batch_beam_search.py:320-330, so its decoder score has no eos term. The t
 always scores eos; Hypothesis.states["decoder"] holds the per-target log-probs, the last one
 being that eos term.) How the mode's accuracy compares with the joint
 search is not measured (no checkpoint or data here).
+
+Shallow fusion (`set_lm`, avsr_amd/ngram_lm.py) adds to that score w_lm * the n-gram LM's log-prob
+of y + [eos] from the <s> state and length_bonus * (len(y) + 1): one avsr_ngram_score_seqs launch
+over an utterance's candidates in the second pass, the terms summed in fp64 on the host with the
+others. The first pass is unchanged; every ctc_weight works (the terms are additive on complete
+sequences). The effect on WER is unmeasured.
 """
 from typing import List
 
 import numpy as np
 import torch
 
+from . import ngram_lm
 from . import ops
 from .decode import Hypothesis
 
@@ -87,6 +94,8 @@ class CTCRescoringSearch:
         self.blank = 0
         self.token_list = token_list
         self.use_dec, self.use_ctc = self.ctc_weight != 1.0, self.ctc_weight != 0.0
+        self.lm, self.w_lm, self.w_len = None, 0.0, 0.0
+        self._lm_dev = ngram_lm.FusionArrays()
 
     def __call__(self, x):
         return self.decode_batch([x])[0]
@@ -96,6 +105,13 @@ class CTCRescoringSearch:
         step, so a phrase list is refused here; None / an empty list is accepted (nothing to clear)"""
         if phrases is not None and len(list(phrases)):
             raise NotImplementedError("hot words: the joint search only (get_beam_search_decoder)")
+
+    def set_lm(self, lm, weight=0.0, length_bonus=0.0):
+        """BatchBeamSearch.set_lm's call form: `lm` (an NgramLM over the model's token ids) at weight
+        `weight` (finite, >= 0) and `length_bonus` (finite) per token of y + [eos], in the second
+        pass; `set_lm(None, 0.0)` clears both"""
+        V = None if self.token_list is None else len(self.token_list)
+        self.lm, self.w_lm, self.w_len = ngram_lm.check_fusion(lm, weight, length_bonus, V, self.sos, self.eos)
 
     # ------------------------------------------------------------------- first pass
     def _ctc_logits(self, eng, xs):
@@ -143,7 +159,8 @@ class CTCRescoringSearch:
     def _enqueue(self, eng, xu, clu, ys):
         """launch the scoring of label sequences ys for one utterance (xu (T, D) memory in the
         engine dtype, clu (T, Vp) its CTC logits); nothing is read back. Returns the device
-        result [n * L1 decoder token log-probs | n CTC nll] and what _finish needs."""
+        result [n * L1 decoder token log-probs | n CTC nll | n * L1 LM token scores], each part only
+        for a scorer in use, and what _finish needs."""
         dev, V = eng.device, eng.V
         T, n = int(xu.shape[0]), len(ys)
         for y in ys:
@@ -189,13 +206,24 @@ class CTCRescoringSearch:
                 rep = clu.unsqueeze(0).expand(n, T, clu.shape[1]).reshape(n * T, clu.shape[1])
                 ops.ctc_fwd(ops.ctc_params(rep, n, T, V, lab.to(dev), llen, ilen, lse.repeat(n), alpha, gamma, nll))
             parts.append(nll)
+        if self.lm is not None:
+            if self.lm.n_vocab != V:
+                raise ValueError(f"the LM's vocabulary of {self.lm.n_vocab} is not the model's {V}")
+            toks = torch.full((n, max(1, Lmax)), -1, dtype=torch.int32)
+            for b, y in enumerate(ys):
+                toks[b, :len(y)] = torch.tensor(y, dtype=torch.int32)
+            lm_out = ops.ngram_score_seqs(self._lm_dev.get(self.lm, dev), toks.to(dev), eos=self.eos)
+            parts.append(lm_out[:, :L1].reshape(-1))
         return torch.cat(parts), dict(ys=ys, L1=L1, feas=feas)
 
     def _finish(self, res, meta):
         """host side: fp64 sums of the fp32 values, the joint score, the ranking"""
         ys, L1, n = meta["ys"], meta["L1"], len(meta["ys"])
-        dec = res[:n * L1].reshape(n, L1) if self.use_dec else None
-        nll = res[-n:] if self.use_ctc else None
+        o = n * L1 if self.use_dec else 0
+        dec = res[:o].reshape(n, L1) if self.use_dec else None
+        nll = res[o:o + n] if self.use_ctc else None
+        o += n if self.use_ctc else 0
+        lms = res[o:o + n * L1].reshape(n, L1) if self.lm is not None else None
         hyps = []
         for b, y in enumerate(ys):
             # avsr_ctc_fwd implements zero_infinity: an infeasible pair comes back as nll 0
@@ -208,6 +236,15 @@ class CTCRescoringSearch:
                 states["decoder"] = torch.from_numpy(np.array(dec[b, :len(y) + 1], dtype=np.float32))
             if c is not None:
                 scores["ctc"] = torch.tensor(c, dtype=torch.float64)
+            if lms is not None:
+                # the fp32 LM score of each of the L + 1 tokens y + [eos], as the kernel gave them
+                states["lm"] = torch.from_numpy(np.array(lms[b, :len(y) + 1], dtype=np.float32))
+                lm_sum = float(np.sum(np.asarray(lms[b, :len(y) + 1], dtype=np.float64)))
+                scores["lm"] = torch.tensor(lm_sum, dtype=torch.float64)
+                score = score + self.w_lm * lm_sum
+            if self.w_len != 0.0:
+                scores["length_bonus"] = torch.tensor(float(len(y) + 1), dtype=torch.float64)
+                score = score + self.w_len * float(len(y) + 1)
             hyps.append(Hypothesis(yseq=torch.tensor([self.sos] + list(y) + [self.eos], dtype=torch.int64),
                                    score=torch.tensor(score, dtype=torch.float64), scores=scores, states=states))
         return rank(hyps)
@@ -259,11 +296,13 @@ class CTCRescoringSearch:
 
 
 def get_rescoring_decoder(model, token_list, ctc_weight=0.1, beam_size=10, token_beam=None, hotwords=None,
-                          hotword_bonus=None):
+                          hotword_bonus=None, lm=None, lm_weight=0.0, length_bonus=0.0):
     """the two-pass counterpart of get_beam_search_decoder — `model` is the E2E
     (`AVHubertAVSR.avsr`); the result has the same call forms (bs(x), decode_batch(xs)). A hot-word
-    list is refused (NotImplementedError): biasing is part of the joint search only"""
+    list is refused (NotImplementedError): biasing is part of the joint search only. lm (an NgramLM),
+    lm_weight and length_bonus: `set_lm` on the result"""
     search = CTCRescoringSearch(model, beam_size=beam_size, token_beam=token_beam, ctc_weight=ctc_weight,
                                 sos=model.sos, eos=model.eos, token_list=token_list)
     search.set_hotwords(hotwords, hotword_bonus)
+    search.set_lm(lm, lm_weight, length_bonus)
     return search

@@ -844,6 +844,19 @@ typedef struct {
    * out_next = next[h][c]; both set together with bonus (next may be NULL with out_next). */
   const float* bonus; const int* next;
   float* out_bonus; int* out_next;
+  /* n-gram LM shallow fusion and the length bonus (lm NULL and w_len 0: off, the selection above
+   * unchanged, arithmetic included). lm / lm_next [n][P+1] as avsr_ngram_step writes them for this
+   * launch's ids. The sum follows the reference's order (batch_beam_search.py:222-245: full scorers
+   * in the order of its scorer dict, then partial scorers, then the running score):
+   *   weighted[h][v] = w_dec*dec + w_len*1 + w_lm*lm[h][c] + w_ctc*(psi - s_prev) [+ bonus] + score[h]
+   * c = the column of v in ids[h], or P for eos. A token outside ids[h] takes an LM term of 0: it
+   * sits at w_ctc*LOGZERO ~ -1e9*w_ctc, where one fp32 step exceeds any LM score. lm_hi: an upper
+   * bound on any lm value (NgramLM.lm_hi), for the bound of the candidates-only pass.
+   * out_lm = the selected (unweighted) LM score, out_lm_next = lm_next[h][c]; for a token outside
+   * ids[h] 0 and -1 (out of range, which avsr_ngram_step reads as the <s> state). */
+  const float* lm; const int* lm_next;
+  float w_lm, w_len, lm_hi;
+  float* out_lm; int* out_lm_next;
 } avsr_beam_select_params;
 int avsr_beam_select(const avsr_beam_select_params* p, void* stream);
 
@@ -882,6 +895,52 @@ typedef struct {
   int* next;                  /* [R][P + C + 1] */
 } avsr_hotword_params;
 int avsr_hotword_step(const avsr_hotword_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * N-gram LM shallow fusion (avsr_amd/ngram_lm.py compiles the model and states the scoring rule;
+ * the reference's counterpart is the "lm" slot of its scorer dict, a host object). A backoff
+ * automaton over token ids in the CSR manner of the hot-word tree: node 0 is the empty context,
+ * node n > 0 a context of 1 .. order-1 tokens with its backoff weight, its fail link (the node of
+ * the context without its oldest token) and its entries [child_off[n], child_off[n+1]) of tok
+ * (ascending) / logp / next; the empty context is dense (uni_logp / uni_next [V]; node 0 has no
+ * span). start = the state of a fresh hypothesis, the node of (sos).
+ *   score(n, v): acc = 0; while n != 0: entry (n, v) exists -> acc + logp, successor next;
+ *                else acc += backoff[n], n = fail[n]; at node 0: acc + uni_logp[v], uni_next[v].
+ * fp32 sums in that order.
+ * avsr_ngram_step, once per search step after the pre-beam and avsr_hotword_step: for row r at
+ *   state[r] (a value outside [0, nodes) is read as start) and each column c < P of ids[r] and the
+ *   eos column c = P: out[r][c] = score, out_next[r][c] = successor. A blank column (padding of
+ *   the hot-word widening) gets 0 and the row's own state. P + 1 <= 64.
+ * avsr_ngram_score_seqs, for complete hypotheses: row b of tokens [n][L] (-1 padded), followed by
+ *   eos, is scored from start: out[b][j] for j <= len(b) (the last one is eos), 0 beyond. */
+enum { AVSR_NGRAM_MAX_ORDER = 6 };
+typedef struct {
+  int order, nodes, V, start;
+  const int* child_off;       /* [nodes + 1] */
+  const float* backoff;       /* [nodes] */
+  const int* fail;            /* [nodes] */
+  const int* tok;             /* [entries]; tok / logp / next all NULL: no entry below the unigram level */
+  const float* logp;          /* [entries] */
+  const int* next;            /* [entries] */
+  const float* uni_logp;      /* [V] */
+  const int* uni_next;        /* [V] */
+} avsr_ngram_lm;
+typedef struct {
+  avsr_ngram_lm lm;
+  int R, P, blank, eos;
+  const int* state;           /* [R] */
+  const int* ids;             /* [R][P] */
+  float* out;                 /* [R][P + 1] */
+  int* out_next;              /* [R][P + 1] */
+} avsr_ngram_params;
+int avsr_ngram_step(const avsr_ngram_params* p, void* stream);
+typedef struct {
+  avsr_ngram_lm lm;
+  int n, L, eos;
+  const int* tokens;          /* [n][L], -1 padded */
+  float* out;                 /* [n][L + 1] */
+} avsr_ngram_seq_params;
+int avsr_ngram_score_seqs(const avsr_ngram_seq_params* p, void* stream);
 
 int avsr_gather_rows(int groups, int n, int64_t row_bytes, const void* src, int64_t src_gstride,
                      int64_t src_rstride, void* dst, int64_t dst_gstride, int64_t dst_rstride,
@@ -936,6 +995,18 @@ typedef struct {
    * ended by the step limit keeps the bonus of an unfinished phrase (its eos is not scored). */
   const float* sel_bonus; const int* sel_next;
   double* shw; double* end_hw; int* node_out;
+  /* n-gram LM (sel_lm NULL: off) and length bonus (slen NULL: off), like the hot-word sums: the
+   * selected unweighted LM score is summed per hypothesis in double (slm[R]) and recorded with an
+   * ended hypothesis (end_lm); slen[R] / end_len count the scored tokens (the length bonus scorer
+   * gives every token 1). lm_state_out[r] = sel_lm_next[r], lm_start for a row of a finished
+   * utterance: the other buffer of the LM state ping-pong. lm_start must be set with sel_lm
+   * (avsr_ngram_lm.start, the node of (sos)): a zeroed field means node 0, the EMPTY context, not
+   * <s>. A hypothesis ended by the step limit
+   * gets the reference's unscored eos: no LM term and no length term for it. */
+  const float* sel_lm; const int* sel_lm_next;
+  double* slm; double* end_lm; int* lm_state_out;
+  double* slen; double* end_len;
+  int lm_start;
 } avsr_beam_post_params;
 typedef struct {
   int U, beam, R, Lmax, slot, sos;
