@@ -145,6 +145,15 @@ class CtcAlignParams(ctypes.Structure):
     ]
 
 
+class CtcNeighborsParams(ctypes.Structure):
+    _fields_ = [
+        ("dtype", _i), ("B", _i), ("T", _i), ("V", _i), ("Lmax", _i), ("blank", _i), ("eos", _i),
+        ("x", _c_p), ("ldx", _i64), ("lse", _c_p), ("labels", _c_p), ("label_len", _c_p), ("in_len", _c_p),
+        ("ws", _c_p), ("sub", _c_p), ("lds", _i64), ("del", _c_p), ("base", _c_p), ("feasible", _c_p),
+        ("lz", _c_p),
+    ]
+
+
 class CtcBeamParams(ctypes.Structure):
     _fields_ = [
         ("U", _i), ("Tm", _i), ("V", _i), ("N", _i), ("C", _i), ("blank", _i), ("eos", _i), ("Lcap", _i),
@@ -344,6 +353,7 @@ SYMBOLS = {
     "avsr_ctc_fwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_bwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_align": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
+    "avsr_ctc_neighbors": ([ctypes.POINTER(CtcNeighborsParams), _c_p], _i),
     "avsr_ctc_beam": ([ctypes.POINTER(CtcBeamParams), _c_p], _i),
     "avsr_loss_finalize": ([_i, _c_p, _i, _c_p, _c_p, _f, _i, _c_p, _c_p], _i),
     "avsr_ew_bwd": ([ctypes.POINTER(EwParams), _c_p], _i),

@@ -100,16 +100,24 @@ def _align_logits(eng, logits, B, T, ys, ilens, blank):
     return ali.cpu().numpy(), score.cpu().numpy(), feas.cpu().numpy()
 
 
+def word_groups(tokens, token_list, space="▁"):
+    """[(word, [indices into tokens])] of sentence-piece ids: a word starts at a piece that begins
+    with `space` (and at the first piece) and runs to its last piece. The one word segmentation of
+    word_times and avsr_amd.confidence.word_confidences, so that their lists zip."""
+    words = []
+    for i, tok in enumerate(tokens):
+        piece = token_list[int(tok)]
+        if piece.startswith(space) or not words:
+            words.append([piece[len(space):] if piece.startswith(space) else piece, [i]])
+        else:
+            words[-1][0] += piece
+            words[-1][1].append(i)
+    return [(w, idx) for w, idx in words]
+
+
 def word_times(spans, token_list, frame_rate=25.0, space="▁"):
     """(word, start_s, end_s) from TokenSpans of sentence pieces: a word starts at a piece that
     begins with `space` (and at the first piece), runs to the end of its last piece; times are
     frames / frame_rate (the config's label_rate)."""
-    words = []
-    for sp in spans:
-        piece = token_list[sp.token]
-        if piece.startswith(space) or not words:
-            words.append([piece[len(space):] if piece.startswith(space) else piece, sp.start, sp.end])
-        else:
-            words[-1][0] += piece
-            words[-1][2] = sp.end
-    return [(w, s / frame_rate, e / frame_rate) for w, s, e in words]
+    return [(w, spans[idx[0]].start / frame_rate, spans[idx[-1]].end / frame_rate)
+            for w, idx in word_groups([sp.token for sp in spans], token_list, space)]

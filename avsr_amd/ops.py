@@ -721,6 +721,40 @@ def ctc_align(x, B, T, V, labels, label_len, in_len, lse, *, blank=0, ali=None, 
     return ali, score, feasible
 
 
+def ctc_neighbors_ws(B, T, Lmax):
+    """bytes of alpha / beta workspace of ctc_neighbors (AVSR_CTC_NEIGHBORS_WS)"""
+    return (B * T * (2 * Lmax + 1) * 2 * 4 + 15) & ~15
+
+
+def ctc_neighbors(x, B, T, V, labels, label_len, in_len, lse, *, blank=0, eos=-1, sub=None, dele=None, base=None,
+                  feasible=None, ws=None, lz=None):
+    """CTC likelihoods of the one-edit neighbours (avsr_ctc_neighbors) of B label sequences over
+    logits x (rows b*T + t, fp32 or bf16) with row log-sum-exp lse: fills / returns sub
+    (B, Lmax, lds >= V) fp32 substitution scores, dele (B, Lmax) deletion scores, base (B,) =
+    log p_ctc(y|x) and feasible (B,) int32; -inf fills as the header states. labels (B, Lmax)
+    int32. lz (B, Lmax) fp32, optional: filled with Z_l - base, the slot normaliser."""
+    dev = x.device
+    Lmax = labels.shape[1]
+    if sub is None:
+        sub = torch.empty(B, Lmax, (V + 7) // 8 * 8, device=dev, dtype=torch.float32)
+    if dele is None:
+        dele = torch.empty(B, Lmax, device=dev, dtype=torch.float32)
+    if base is None:
+        base = torch.empty(B, device=dev, dtype=torch.float32)
+    if feasible is None:
+        feasible = torch.empty(B, device=dev, dtype=torch.int32)
+    if sub.dtype != torch.float32 or sub.stride(2) != 1 or sub.stride(0) != Lmax * sub.stride(1) \
+            or tuple(sub.shape[:2]) != (B, Lmax) or not dele.is_contiguous() or (lz is not None and not lz.is_contiguous()):
+        raise TypeError("ctc_neighbors: sub (B, Lmax, lds) fp32 with dense rows, dele / lz contiguous")
+    if ws is None and 2 * Lmax + 1 <= 1024:      # beyond the bound the launcher returns the shape error
+        ws = torch.empty(max(16, ctc_neighbors_ws(B, T, Lmax)), device=dev, dtype=torch.uint8)
+    _call("avsr_ctc_neighbors", L.fill(L.CtcNeighborsParams, dtype=dtype_code(x), B=B, T=T, V=V, Lmax=Lmax,
+                                        blank=blank, eos=eos, x=x, ldx=x.stride(0), lse=lse, labels=labels,
+                                        label_len=label_len, in_len=in_len, ws=ws, sub=sub, lds=sub.stride(1),
+                                        base=base, feasible=feasible, lz=lz, **{"del": dele}))
+    return sub, dele, base, feasible
+
+
 def token_logp(x, V, target, out=None, lse=None):
     """out[row] = float(x[row][target[row]]) - lse[row] in fp32, 0 where target[row] = -1: the
     log-probability of each row's target under softmax(x[row][:V]) (x fp32 or bf16, target int32).

@@ -73,6 +73,47 @@ def rank(hyps):
     return sorted(hyps, key=lambda h: -float(h.score))
 
 
+def ctc_logits(eng, xs):
+    """padded memory xp (U, Tm, D) in the engine dtype and CTC logits cl (U*Tm, Vp). The CTC
+    head runs per utterance (M = T_u rows, as BatchBeamSearch.decode_batch does): the few-row
+    and tiled GEMM cores round differently, so one launch over all U * Tm rows would make an
+    utterance's result depend on the batch. (Shared with avsr_amd/confidence.py.)"""
+    dev, D = eng.device, eng.dD
+    Ts = [int(x.shape[0]) for x in xs]
+    Tm = max(Ts + [1])
+    xp = torch.zeros(len(xs), Tm, D, device=dev, dtype=eng.dtype)
+    cl = torch.zeros(len(xs) * Tm, eng.Vp, device=dev, dtype=eng.dtype)
+    for u, x in enumerate(xs):
+        if Ts[u] == 0:
+            continue
+        ops.cast(x.to(dev).reshape(Ts[u], D).contiguous(), xp[u, :Ts[u]])
+        ops.linear_fwd(xp[u, :Ts[u]], eng.w("ctc.ctc_lo.weight"), eng.arena.master("ctc.ctc_lo.bias"),
+                       out=cl[u * Tm:u * Tm + Ts[u], :eng.V])
+    return xp, cl, Ts, Tm
+
+
+def decoder_token_logp(eng, xu, ys, sos, eos):
+    """fp32 log-probabilities of the targets y + [eos] of each label sequence in ys under the
+    attention decoder, for one utterance (xu (T, D) memory in the engine dtype): ONE
+    teacher-forced pass over [sos] + y (rows padded with eos: the causal mask keeps earlier
+    positions independent of the padding); targets y + [eos], -1 on padding (log-prob 0 there).
+    Returns the device tensor (len(ys) * L1,), L1 = longest y + 1; nothing is read back. (The
+    second pass of two-pass decoding and avsr_amd/confidence.py both score through this.)"""
+    dev = eng.device
+    T, n = int(xu.shape[0]), len(ys)
+    L1 = max(len(y) for y in ys) + 1
+    ys_in = torch.full((n, L1), eos, dtype=torch.int32)
+    tgt = torch.full((n, L1), -1, dtype=torch.int32)
+    for b, y in enumerate(ys):
+        ys_in[b, 0] = sos
+        ys_in[b, 1:len(y) + 1] = torch.tensor(y, dtype=torch.int32)
+        tgt[b, :len(y)] = torch.tensor(y, dtype=torch.int32)
+        tgt[b, len(y)] = eos
+    from .surface import _teacher_forced
+    logits, _ = _teacher_forced(eng, ys_in.to(dev), xu.unsqueeze(0).expand(n, T, xu.shape[1]), None)
+    return ops.token_logp(logits, eng.V, tgt.reshape(-1).to(dev))
+
+
 class CTCRescoringSearch:
     """CTC prefix beam search (beam_size prefixes, token_beam candidate tokens per frame) and
     attention rescoring with the decoder + CTC scorers of an E2E model on its HIP engine."""
@@ -115,22 +156,7 @@ class CTCRescoringSearch:
 
     # ------------------------------------------------------------------- first pass
     def _ctc_logits(self, eng, xs):
-        """padded memory xp (U, Tm, D) in the engine dtype and CTC logits cl (U*Tm, Vp). The CTC
-        head runs per utterance (M = T_u rows, as BatchBeamSearch.decode_batch does): the few-row
-        and tiled GEMM cores round differently, so one launch over all U * Tm rows would make an
-        utterance's result depend on the batch."""
-        dev, D = eng.device, eng.dD
-        Ts = [int(x.shape[0]) for x in xs]
-        Tm = max(Ts + [1])
-        xp = torch.zeros(len(xs), Tm, D, device=dev, dtype=eng.dtype)
-        cl = torch.zeros(len(xs) * Tm, eng.Vp, device=dev, dtype=eng.dtype)
-        for u, x in enumerate(xs):
-            if Ts[u] == 0:
-                continue
-            ops.cast(x.to(dev).reshape(Ts[u], D).contiguous(), xp[u, :Ts[u]])
-            ops.linear_fwd(xp[u, :Ts[u]], eng.w("ctc.ctc_lo.weight"), eng.arena.master("ctc.ctc_lo.bias"),
-                           out=cl[u * Tm:u * Tm + Ts[u], :eng.V])
-        return xp, cl, Ts, Tm
+        return ctc_logits(eng, xs)
 
     def _first_pass(self, eng, cl, Ts, Tm):
         """log-softmax + per-frame top token_beam of every row, then ONE avsr_ctc_beam launch for
@@ -174,18 +200,7 @@ class CTCRescoringSearch:
         L1 = Lmax + 1
         parts = []
         if self.use_dec:
-            # one teacher-forced pass over [sos] + y (rows padded with eos: the causal mask keeps
-            # earlier positions independent of the padding); targets y + [eos], -1 on padding
-            ys_in = torch.full((n, L1), self.eos, dtype=torch.int32)
-            tgt = torch.full((n, L1), -1, dtype=torch.int32)
-            for b, y in enumerate(ys):
-                ys_in[b, 0] = self.sos
-                ys_in[b, 1:len(y) + 1] = torch.tensor(y, dtype=torch.int32)
-                tgt[b, :len(y)] = torch.tensor(y, dtype=torch.int32)
-                tgt[b, len(y)] = self.eos
-            from .surface import _teacher_forced
-            logits, _ = _teacher_forced(eng, ys_in.to(dev), xu.unsqueeze(0).expand(n, T, xu.shape[1]), None)
-            parts.append(ops.token_logp(logits, V, tgt.reshape(-1).to(dev)))
+            parts.append(decoder_token_logp(eng, xu, ys, self.sos, self.eos))
         feas = [ctc_feasible(T, y) for y in ys]
         if self.use_ctc:
             # exact CTC likelihood of every hypothesis in ONE launch (the loss path's row-lse prologue

@@ -570,6 +570,67 @@ typedef struct {
 int avsr_ctc_align(const avsr_ctc_align_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * avsr_ctc_neighbors: the exact CTC log-likelihood of every ONE-EDIT NEIGHBOUR of a label
+ *   sequence, for B utterances in one call (the reference has no counterpart; token and word
+ *   confidences, avsr_amd/confidence.py). For y = y_1..y_L over n = min(in_len[b], T) frames and a
+ *   slot l, the neighbours are y with y_l replaced by v, for every vocabulary token v, and y with
+ *   y_l deleted. Setup, all in fp32:
+ *     e(t,k) = float(x[t][k]) - lse[t]
+ *     ext = blank, y_1, blank, ..., y_L, blank with S = 2L + 1 states; y_j sits at state 2j - 1
+ *     alpha_t(s), beta_t(s): the CTC forward / backward variables of y; beta_t(s) includes
+ *     e(t, ext_s); frames run 0..n-1
+ *   Substitution at slot l, state m = 2l - 1, token v (v != blank, v != eos, 0 <= v < V):
+ *     a_0 = e(0,v) if l == 1 else -inf
+ *     a_t = e(t,v) + LSE( a_{t-1}, alpha_{t-1}(m-1), [l >= 2 and v != y_{l-1}] alpha_{t-1}(m-2) )
+ *     sub[l][v] = LSE_{t <= n-2}( a_t + LSE( beta_{t+1}(m+1), [l < L and v != y_{l+1}] beta_{t+1}(m+2) ) )
+ *                 (+) a_{n-1} if l == L
+ *   so sub[l][v] = log p_ctc(y_1..y_{l-1}, v, y_{l+1}..y_L | x), and sub[l][y_l] = log p_ctc(y | x)
+ *   for every l (up to rounding). Deletion at slot l, del[l] = log p_ctc(y without y_l | x):
+ *     1 < l < L:  LSE_{t <= n-2}( LSE( alpha_t(2l-2), [y_{l-1} != y_{l+1}] alpha_t(2l-3) ) + beta_{t+1}(2l+1) )
+ *     l = 1 < L:  the same without the alpha_t(2l-3) term, (+) beta_0(3)
+ *     l = L > 1:  LSE( alpha_{n-1}(2L-2), alpha_{n-1}(2L-3) )
+ *     L = 1:      alpha_{n-1}(0), the all-blank path
+ *   A neighbour with no CTC path (a substitute that creates an adjacent repeat the frames cannot
+ *   separate) is -inf exactly, not an error: unreachable states are -inf, never a large negative.
+ *   Slot posterior: Z_l = LSE( sub[l][v] over allowed v, del[l] ); conf_ctc(l) =
+ *   exp(sub[l][y_l] - Z_l) in (0, 1]; an alternative v has exp(sub[l][v] - Z_l), the deletion
+ *   exp(del[l] - Z_l). lz[b][l] (optional, NULL: not computed) = Z_l - base[b], accumulated
+ *   relative to the row maximum so that it carries fp32 rounding of a value near 0, not of Z_l.
+ *   Insertions (a token between two slots) are not neighbours here.
+ *   Outputs, slots 0-based in memory (slot l above is row l - 1); EVERY element is written:
+ *     sub[b][l][0..lds): -inf in the blank and eos columns (eos = -1: none excluded), in columns
+ *       V..lds-1 and in rows l >= label_len[b];  del[b][l], lz[b][l]: -inf for l >= label_len[b];
+ *     base[b] = log p_ctc(y | x);  feasible[b] = 1 if the utterance was computed.
+ *   feasible[b] = 0, base[b] = 0 and -inf everywhere else when in_len[b] <= 0, when y has no path
+ *   (in_len[b] < L + number of adjacent equal labels), when a label is outside [0, V) or equals
+ *   blank, or when label_len[b] is outside [0, Lmax] (avsr_ctc_align's rules). label_len[b] = 0 is
+ *   feasible and has no slots. Frames t >= in_len[b] and columns >= V of x are never read.
+ *   Utterances do not influence each other, and the result for an utterance is a function of its
+ *   own inputs alone: no atomics, every reduction in a fixed order (time ascending per (slot, v);
+ *   lz by a fixed tree over the row).
+ *   ws: caller-owned alpha and beta, AVSR_CTC_NEIGHBORS_WS(B, T, Lmax) BYTES ([B][T][2*Lmax+1]
+ *   floats each), 16-byte aligned (AVSR_E_ALIGN otherwise); contents on entry are irrelevant.
+ *   Limits: 2*Lmax + 1 <= 1024 (AVSR_E_SHAPE beyond it) as avsr_ctc_fwd; T is not bounded;
+ *   lds >= V. No allocation, no host sync.
+ * ------------------------------------------------------------------------------------ */
+typedef struct {
+  int dtype, B, T, V, Lmax, blank, eos;   /* dtype of x: AVSR_F32 or AVSR_BF16; eos -1: none */
+  const void* x; int64_t ldx;          /* logits, rows b*T + t, V valid columns */
+  const float* lse;                    /* [B*T] */
+  const int* labels;                   /* [B][Lmax] */
+  const int* label_len; const int* in_len;   /* [B] */
+  void* ws;                            /* AVSR_CTC_NEIGHBORS_WS(B, T, Lmax) bytes */
+  float* sub; int64_t lds;             /* [B][Lmax][lds] */
+  float* del;                          /* [B][Lmax] */
+  float* base;                         /* [B] */
+  int* feasible;                       /* [B] */
+  float* lz;                           /* [B][Lmax] or NULL */
+} avsr_ctc_neighbors_params;
+#define AVSR_CTC_NEIGHBORS_WS(B, T, Lmax) \
+  ((((int64_t)(B) * (T) * (2 * (int64_t)(Lmax) + 1) * 2 * 4) + 15) & ~(int64_t)15)
+int avsr_ctc_neighbors(const avsr_ctc_neighbors_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * avsr_ctc_beam: time-synchronous CTC prefix beam search (the first pass of two-pass decoding,
  *   avsr_amd/rescore.py; the reference has no such search) of U utterances in one launch, over
  *   fp32 CTC log-probs logp (rows u*Tm + t, ldp floats apart) and C candidate tokens per frame
