@@ -162,6 +162,14 @@ class CtcBeamParams(ctypes.Structure):
     ]
 
 
+class CtcKwsParams(ctypes.Structure):
+    _fields_ = [
+        ("U", _i), ("Tm", _i), ("V", _i), ("K", _i), ("Lmax", _i), ("blank", _i),
+        ("logp", _c_p), ("ldp", _i64), ("tlen", _c_p), ("top", _c_p), ("labels", _c_p), ("label_len", _c_p),
+        ("score", _c_p), ("start", _c_p), ("end", _c_p), ("trace", _c_p), ("tstart", _c_p),
+    ]
+
+
 class EwParams(ctypes.Structure):
     _fields_ = [
         ("dtype", _i), ("rows", _i), ("N", _i), ("dy", _c_p), ("lddy", _i64), ("out", _c_p), ("ldout", _i64),
@@ -355,6 +363,7 @@ SYMBOLS = {
     "avsr_ctc_align": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
     "avsr_ctc_neighbors": ([ctypes.POINTER(CtcNeighborsParams), _c_p], _i),
     "avsr_ctc_beam": ([ctypes.POINTER(CtcBeamParams), _c_p], _i),
+    "avsr_ctc_kws": ([ctypes.POINTER(CtcKwsParams), _c_p], _i),
     "avsr_loss_finalize": ([_i, _c_p, _i, _c_p, _c_p, _f, _i, _c_p, _c_p], _i),
     "avsr_ew_bwd": ([ctypes.POINTER(EwParams), _c_p], _i),
     "avsr_colsum_defer": ([_i], _i),

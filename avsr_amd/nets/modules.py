@@ -276,6 +276,10 @@ class CTCHead(_Holder):
         from ..surface import ctc_forced_align_batch
         return ctc_forced_align_batch(_e2e(self), hs_pad, ys_pad, ilens, blank_id)
 
+    def spot_keywords(self, h, keywords, threshold=None, occurrences=False):
+        from ..surface import ctc_spot_keywords
+        return ctc_spot_keywords(_e2e(self), h, keywords, threshold, occurrences)
+
 
 CTC = CTCHead
 

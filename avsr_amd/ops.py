@@ -808,6 +808,53 @@ def ctc_beam(logp, tlen, cand, N, *, blank, eos, Lcap=None, ws=None):
     return n_out, tokens, length, score
 
 
+CTC_KWS_LMAX = 32          # avsr_ctc_kws: pieces per keyword (2L - 1 <= 63 states, one per lane)
+
+
+def ctc_kws(logp, tlen, top, labels, label_len, *, blank, trace=False, score=None, start=None, end=None,
+            trace_out=None, tstart_out=None):
+    """Keyword spotting on CTC posteriors (avsr_ctc_kws), K keywords x U utterances in one launch:
+    logp (U, Tm, V) fp32 CTC log-probs, tlen (U,) int32 frames, top (U, Tm) int32 row argmax
+    (log_softmax_topk with K = 1) or None for no filler, labels (K, Lmax) int32, label_len (K,)
+    int32. Returns device tensors score (U, K) fp32, start, end (U, K) int32 (the keyword's best
+    occurrence spans frames [start, end); -inf / -1 / -1 where it has no path), and with
+    trace=True also trace (U, K, Tm) fp32 and tstart (U, K, Tm) int32, the score and start of the
+    best occurrence ENDING at each frame. Outputs may be preallocated (score / start / end,
+    trace_out / tstart_out; giving only one of the last two is the launcher's argument error)."""
+    U, Tm, V = logp.shape
+    if logp.dtype != torch.float32 or tlen.dtype != torch.int32 or labels.dtype != torch.int32 \
+            or label_len.dtype != torch.int32 or (top is not None and top.dtype != torch.int32):
+        raise TypeError("ctc_kws: logp fp32, tlen, top, labels and label_len int32")
+    if labels.dim() != 2:
+        raise ValueError("ctc_kws: labels (K, Lmax)")
+    K, Lmax = labels.shape
+    if logp.stride(2) != 1 or logp.stride(0) != Tm * logp.stride(1) or tlen.numel() != U or not labels.is_contiguous() \
+            or label_len.numel() != K or (top is not None and (top.numel() != U * Tm or not top.is_contiguous())):
+        raise ValueError("ctc_kws: logp rows u*Tm + t, tlen (U,), top (U, Tm) and labels (K, Lmax) contiguous, "
+                         "label_len (K,)")
+    dev = logp.device
+    if score is None:
+        score = torch.empty(U, K, device=dev, dtype=torch.float32)
+    if start is None:
+        start = torch.empty(U, K, device=dev, dtype=torch.int32)
+    if end is None:
+        end = torch.empty(U, K, device=dev, dtype=torch.int32)
+    if trace and trace_out is None and tstart_out is None:
+        trace_out = torch.empty(U, K, Tm, device=dev, dtype=torch.float32)
+        tstart_out = torch.empty(U, K, Tm, device=dev, dtype=torch.int32)
+    for name, t, dt, shape in (("score", score, torch.float32, (U, K)), ("start", start, torch.int32, (U, K)),
+                               ("end", end, torch.int32, (U, K)), ("trace_out", trace_out, torch.float32, (U, K, Tm)),
+                               ("tstart_out", tstart_out, torch.int32, (U, K, Tm))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise TypeError(f"ctc_kws: {name} {shape} {dt} contiguous")
+    _call("avsr_ctc_kws", L.fill(L.CtcKwsParams, U=U, Tm=Tm, V=V, K=K, Lmax=Lmax, blank=blank, logp=logp,
+                                  ldp=logp.stride(1), tlen=tlen, top=top, labels=labels, label_len=label_len,
+                                  score=score, start=start, end=end, trace=trace_out, tstart=tstart_out))
+    if trace_out is not None:
+        return score, start, end, trace_out, tstart_out
+    return score, start, end
+
+
 def loss_finalize(B, nll, row_loss, row_correct, mtlalpha, out, att_per_token=False):
     """att_per_token: the attention loss divides by the number of target tokens
     (transformer_length_normalized_loss) instead of B"""

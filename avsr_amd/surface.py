@@ -9,6 +9,7 @@ Callers of the reference reach the model through three sub-modules of `AVHubertA
         src/nets/backend/transformer/decoder.py:122-227
   ctc.forward / log_softmax / softmax / argmax / forced_align / forced_align_batch
         src/nets/backend/ctc.py:83-328
+  (and ctc.spot_keywords, which the reference does not have: avsr_amd/kws.py)
 
 The functions here implement those entry points on an `Engine` (avsr_amd.engine); the
 parameter-holder modules of avsr_amd.nets.modules forward to them. Semantics follow the
@@ -363,3 +364,21 @@ def ctc_forced_align(e2e, h, y, blank_id=0):
     ys = [[int(t) for t in torch.as_tensor(y).reshape(-1).tolist()]]
     ali, _, feas = _align_logits(eng, _ctc_logits(eng, h), 1, T, ys, [T], blank_id)
     return _aligned_or_raise(ali, feas, [T], "forced_align")[0].tolist()
+
+
+@torch.no_grad()
+def ctc_spot_keywords(e2e, h, keywords, threshold=None, occurrences=False):
+    """CTCHead.spot_keywords (the reference has no counterpart; the call form of forced_align):
+    h hidden states (T, D) or (1, T, D), through ctc_lo on the engine; keywords a list of token-id
+    lists -> the KeywordHits of avsr_amd.kws.spot_batch for this one utterance, sorted by start."""
+    from .kws import _spot_logits, check_keywords
+    eng = e2e.engine()
+    if h.dim() == 2:
+        h = h.unsqueeze(0)
+    if h.dim() != 3 or h.shape[0] != 1:
+        raise ValueError(f"spot_keywords takes (T, D) or (1, T, D) hidden states, got {tuple(h.shape)}")
+    kws = check_keywords(keywords, eng.V, e2e.blank, e2e.eos)
+    T = h.shape[1]
+    if T == 0:
+        return []
+    return _spot_logits(eng, _ctc_logits(eng, h), [T], T, kws, e2e.blank, threshold, occurrences)[0]

@@ -681,6 +681,56 @@ typedef struct {
 int avsr_ctc_beam(const avsr_ctc_beam_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * avsr_ctc_kws: keyword spotting on CTC posteriors (avsr_amd/kws.py; the reference has no
+ *   counterpart): the CTC Viterbi of each of K keywords with a FREE START and a FREE END inside
+ *   each of U utterances, one launch, over fp32 CTC log-probs logp (rows u*Tm + t, ldp floats
+ *   apart, V valid columns, as for avsr_ctc_beam). For a pair (u, k), all in fp32, with
+ *   y = labels[k][0..L), L = label_len[k], n = min(tlen[u], Tm):
+ *     ext = y1, blank, y2, blank, ..., yL              S = 2L - 1 states (no outer blanks)
+ *     f(t)   = logp[t][top[t]]  (0 when top == NULL)    the filler: the frame's best token
+ *     r(t,s) = logp[t][ext_s] - f(t)                    a log-ratio, <= 0 with a filler
+ *     skip(s) = s >= 2 and ext_s != blank and ext_s != ext_{s-2}
+ *     before frame 0 every state is -inf with start -1; for t = 0 .. n-1:
+ *       m, b = d[t-1][s], st[t-1][s]
+ *       if s >= 1 and d[t-1][s-1] > m: m, b = d[t-1][s-1], st[t-1][s-1]
+ *       if skip(s) and d[t-1][s-2] > m: m, b = d[t-1][s-2], st[t-1][s-2]
+ *       if s == 0 and 0 > m:            m, b = 0, t     the keyword may begin at any frame; the
+ *                                                       filler before it costs nothing
+ *       d[t][s] = m + r(t,s);  st[t][s] = b  (-1 where d[t][s] is -inf)
+ *     score = max over t of d[t][S-1]; on ties the LAST such t wins (update on >=)
+ *     end = t* + 1;  start = st[t*][S-1]               the keyword spans frames [start, end)
+ *   Every comparison is strict and the order is stay, s-1, s-2, enter, so a run of frames that
+ *   tie (the keyword's own argmax run) falls wholly inside the span. The only arithmetic is one
+ *   subtraction and one addition per cell: a float32 host DP reproduces score, start and end bit
+ *   for bit. With a filler the score is the log-ratio of the keyword's best path over its span to
+ *   the frame-wise best tokens over the same span (0 when the keyword IS the greedy reading).
+ *   top[u*Tm + t] is the row argmax (avsr_log_softmax_topk with K = 1); a value outside [0, V) is
+ *   read as the nearest valid column.
+ *   Outputs, EVERY element is written: score[u][k], start[u][k], end[u][k]; optional
+ *   trace[u][k][t] = d[t][S-1] and tstart[u][k][t] = st[t][S-1] (both or neither; -inf / -1 for
+ *   t >= n). A pair with no path gets score = -inf, start = end = -1 (trace -inf, tstart -1):
+ *   n <= 0, n < L + the number of adjacent equal labels, L outside [1, Lmax], a label outside
+ *   [0, V) or equal to blank. Other pairs of the launch are unaffected.
+ *   Frames t >= tlen[u], columns >= V and labels[k][l >= L] are never read. Pairs do not
+ *   influence each other (one wavefront each, one state per lane, no LDS); no atomics, no
+ *   allocation, no host sync.
+ *   Limits: 1 <= Lmax <= 32 (S <= 63: one state per lane), K >= 1, 1 <= U <= 65535, Tm >= 1,
+ *   AVSR_E_SHAPE beyond them; p NULL, a NULL required pointer, blank outside [0, V), ldp < V, or
+ *   trace given without tstart (or the reverse): AVSR_E_ARG.
+ * ------------------------------------------------------------------------------------ */
+typedef struct {
+  int U, Tm, V, K, Lmax, blank;
+  const float* logp; int64_t ldp;      /* [U*Tm][ldp], V valid columns */
+  const int* tlen;                     /* [U] */
+  const int* top;                      /* [U*Tm] row argmax, or NULL: no filler */
+  const int* labels;                   /* [K][Lmax] */
+  const int* label_len;                /* [K] */
+  float* score; int* start; int* end;  /* [U][K] */
+  float* trace; int* tstart;           /* [U][K][Tm], or both NULL */
+} avsr_ctc_kws_params;
+int avsr_ctc_kws(const avsr_ctc_kws_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Elementwise / data-movement kernels around the GEMMs.
  * avsr_ew_bwd:     out = alpha * dy * dropmask(drop_p, seed; idx = row*N + col) * act'(gate),
  *                  db[n] += sum_rows out  (bias gradients of the Linear layers; out optional)
