@@ -361,6 +361,7 @@ SYMBOLS = {
     "avsr_ctc_fwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_bwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_align": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
+    "avsr_ctc_align_long": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
     "avsr_ctc_neighbors": ([ctypes.POINTER(CtcNeighborsParams), _c_p], _i),
     "avsr_ctc_beam": ([ctypes.POINTER(CtcBeamParams), _c_p], _i),
     "avsr_ctc_kws": ([ctypes.POINTER(CtcKwsParams), _c_p], _i),

@@ -721,6 +721,36 @@ def ctc_align(x, B, T, V, labels, label_len, in_len, lse, *, blank=0, ali=None, 
     return ali, score, feasible
 
 
+CTC_ALIGN_LONG_LMAX = 16383    # avsr_ctc_align_long: labels per recording (AVSR_CTC_ALIGN_LONG_LMAX)
+
+
+def ctc_align_long_ws(B, T, Lmax):
+    """bytes of back-pointer workspace of ctc_align_long (AVSR_CTC_ALIGN_LONG_WS): 2 bits per
+    (b, t, state), a row padded to 16 bytes"""
+    return B * T * (((2 * Lmax + 1 + 63) >> 6) << 4)
+
+
+def ctc_align_long(x, B, T, V, labels, label_len, in_len, lse, *, blank=0, ali=None, score=None, feasible=None,
+                   ws=None):
+    """ctc_align for whole recordings (avsr_ctc_align_long): the same arguments and results, label
+    sequences of up to CTC_ALIGN_LONG_LMAX tokens; ws of ctc_align_long_ws(B, T, Lmax) bytes,
+    16-byte aligned."""
+    dev = x.device
+    Lmax = labels.shape[1]
+    if ali is None:
+        ali = torch.empty(B, T, device=dev, dtype=torch.int32)
+    if score is None:
+        score = torch.empty(B, device=dev, dtype=torch.float32)
+    if feasible is None:
+        feasible = torch.empty(B, device=dev, dtype=torch.int32)
+    if ws is None and Lmax <= CTC_ALIGN_LONG_LMAX:      # beyond the bound the launcher returns the shape error
+        ws = torch.empty(max(16, ctc_align_long_ws(B, T, Lmax)), device=dev, dtype=torch.uint8)
+    _call("avsr_ctc_align_long", L.fill(L.CtcAlignParams, dtype=dtype_code(x), B=B, T=T, V=V, Lmax=Lmax, blank=blank,
+                                         x=x, ldx=x.stride(0), lse=lse, labels=labels, label_len=label_len,
+                                         in_len=in_len, ws=ws, ali=ali, score=score, feasible=feasible))
+    return ali, score, feasible
+
+
 def ctc_neighbors_ws(B, T, Lmax):
     """bytes of alpha / beta workspace of ctc_neighbors (AVSR_CTC_NEIGHBORS_WS)"""
     return (B * T * (2 * Lmax + 1) * 2 * 4 + 15) & ~15

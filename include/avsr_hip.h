@@ -570,6 +570,24 @@ typedef struct {
 int avsr_ctc_align(const avsr_ctc_align_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * avsr_ctc_align_long: avsr_ctc_align for whole recordings (avsr_amd/longform.py): the same
+ *   parameter struct and the same definition -- emissions, recursion, skip rule, first-maximum
+ *   back-pointer and final state, the ali / score / feasible fills and every infeasibility rule
+ *   (label_len[b] outside [0, Lmax] included) -- so a float32 host Viterbi reproduces ali and
+ *   score bit for bit, and where both kernels apply they return the same. The differences:
+ *   Label-length bound: Lmax <= AVSR_CTC_ALIGN_LONG_LMAX = 16383 (S <= 32767 states;
+ *   AVSR_E_SHAPE beyond it); T is not bounded. One 1024-thread workgroup per recording.
+ *   ws: AVSR_CTC_ALIGN_LONG_WS(B, T, Lmax) BYTES: back-pointers of 2 bits per (b, t, state), a
+ *   (b, t) row padded to 16 bytes (T = 30000, Lmax = 6000: 90 MB); 16-byte aligned,
+ *   AVSR_E_ALIGN otherwise; contents on entry are irrelevant.
+ *   No allocation, no sync, no atomics.
+ * ------------------------------------------------------------------------------------ */
+#define AVSR_CTC_ALIGN_LONG_LMAX 16383
+#define AVSR_CTC_ALIGN_LONG_WS(B, T, Lmax) \
+  ((int64_t)(B) * (T) * (((2 * (int64_t)(Lmax) + 1 + 63) >> 6) << 4))
+int avsr_ctc_align_long(const avsr_ctc_align_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * avsr_ctc_neighbors: the exact CTC log-likelihood of every ONE-EDIT NEIGHBOUR of a label
  *   sequence, for B utterances in one call (the reference has no counterpart; token and word
  *   confidences, avsr_amd/confidence.py). For y = y_1..y_L over n = min(in_len[b], T) frames and a
