@@ -14,6 +14,9 @@ per-utterance cross-attention K/V, pre-beam top-k, CTC prefix recursion, weighte
 top-beam, running scores, back-pointers, ended-hypothesis records, end detection), and every
 step after the first is one HIP-graph replay; the host reads a finished-utterance count every
 8 steps and the history once at the end — the reference synchronises per hypothesis.
+The step's kernels, one family per file of csrc/: decode_softmax.hip (log-softmax, top-k),
+dec_attn.hip, ctc_prefix.hip, beam.hip (selection, bookkeeping, state gather), and hotword.hip /
+ngram.hip for the two optional scorers below.
 
 A stream of utterances of unequal length goes through a `DecodeSession` (`bs.stream()`,
 `bs.decode_stream(xs)`): a fixed number of utterance slots whose graphs are captured once, a
@@ -91,7 +94,7 @@ class Hypothesis(NamedTuple):
 
 def end_detect(ended_hyps, i, M=3, D_end=D_END):
     """src/nets/e2e_asr_common.py:18-48 (host form; the search evaluates it on the device,
-    decode.hip beam_post_kernel, over the per-length best ended scores)"""
+    beam.hip beam_post_kernel, over the per-length best ended scores)"""
     if len(ended_hyps) == 0:
         return False
     count = 0
@@ -212,7 +215,7 @@ class BatchBeamSearch:
         ar = eng.arena
         D, H, R = eng.dD, eng.dH, st["R"]
         pos, cache, anc = st["pos"], st["cache"], st["anc_in"]
-        pr = "rowpos" in st                     # a session's state: pos holds one position per row
+        pr = st["per_row"]                      # a session's state: pos holds one position per row
         x = eng._e(R, D)
         ops.embed_fwd(st["tok"], eng.w("decoder.embed.0.weight"), eng._pe, math.sqrt(D), x, 1, pe_row=pos, per_row=pr)
         Tm = st["Tm"]
@@ -285,18 +288,15 @@ class BatchBeamSearch:
                 ff1=f(eng.w(ff + "w_1.weight"), ar.master(ff + "w_1.bias"), p + "norm3")))
         return out
 
-    def _ctc_full_vocab(self, st, r_prev):
-        """ctc_weight = 1: psi of every token (chunks of 64 ids through the prefix kernel), then
-        the row's top-P tokens by psi into st["ids"] (the kernel's psi of a token does not depend
-        on the other ids of its launch)"""
-        R, V = st["R"], self.n_vocab
-        kw = dict(n=R, out_len=0, out_len_dev=st["pos"], per_row="rowpos" in st, blank=self.blank, eos=self.eos,
-                  uidx=st["uidx"], tlen=st["tlen"])
+    def _ctc_full_vocab(self, st, r_prev, ctc_kw):
+        """ctc_weight = 1: psi of every token (chunks of 64 ids through the prefix kernel, ctc_kw the
+        step's ctc_prefix keywords), then the row's top-P tokens by psi into st["ids"] (the kernel's
+        psi of a token does not depend on the other ids of its launch)"""
         pf = st["psi_full"]
         for c in range(st["vchunks"].shape[0]):
-            ops.ctc_prefix(st["logp"], r_prev, st["tok"], st["vchunks"][c], st["r_scr"], st["psi_c"], **kw)
+            ops.ctc_prefix(st["logp"], r_prev, st["tok"], st["vchunks"][c], st["r_scr"], st["psi_c"], **ctc_kw)
             pf[:, c * 64:(c + 1) * 64].copy_(st["psi_c"][:, :64])
-        ops.row_topk(pf, V, self.pre_beam_size, st["ids"])
+        ops.row_topk(pf, self.n_vocab, self.pre_beam_size, st["ids"])
 
     def _step(self, eng, st, first, k):
         """one search step on the device (no host sync): decoder, pre-beam, CTC prefix scores,
@@ -304,10 +304,11 @@ class BatchBeamSearch:
         and CTC-state ping-pong buffers (read k, write 1 - k)."""
         R, P, beam = st["R"], self.pre_beam_size, self.beam_size
         st["anc_in"] = st["anc"][k]
-        ops.beam_step_prep(R, st["pos"], st["anc"][k], st["klen_self"], per_row="rowpos" in st)
+        ops.beam_step_prep(R, st["pos"], st["anc"][k], st["klen_self"], per_row=st["per_row"])
         # decoder log-probs + the pre-beam ids; without a decoder scorer its score is 0
         dec = self._decoder_step(eng, st) if self.use_dec else st["dec0"]
-        ids, hw, sel_hw, post_hw = st["ids"], st.get("hw"), {}, {}
+        # sel_extra / post_extra: what hot words, the LM and the length bonus add to beam_select / beam_post
+        ids, hw, sel_extra, post_extra = st["ids"], st.get("hw"), {}, {}
         if hw is not None:
             # hot words: the candidates widen by the continuations of each row's tree node; bonus and
             # successor node per column (node ping-pong: read k, beam_post writes 1 - k)
@@ -315,33 +316,33 @@ class BatchBeamSearch:
             ops.hotword_step(hw["tree"], hw["node"][k], st["ids"], ids, hw["bonus"], hw["next"], beta=hw["beta"],
                              blank=self.blank, eos=self.eos)
             P = ids.shape[1]
-            sel_hw = dict(bonus=hw["bonus"], nxt=hw["next"])
+            sel_extra = dict(bonus=hw["bonus"], nxt=hw["next"])
         lm = st.get("lm")
         if lm is not None and "arrays" in lm:
             # the LM scores the widened ids (continuation columns too) and eos from each row's state
             # (state ping-pong: read k, beam_post writes 1 - k)
             ops.ngram_step(lm["arrays"], lm["state"][k], ids, lm["score"], lm["next"], blank=self.blank, eos=self.eos)
-            sel_hw.update(lm=lm["score"], lm_next=lm["next"], w_lm=self.w_lm, lm_hi=lm["arrays"]["lm_hi"])
+            sel_extra.update(lm=lm["score"], lm_next=lm["next"], w_lm=self.w_lm, lm_hi=lm["arrays"]["lm_hi"])
         if lm is not None:
-            sel_hw["w_len"] = self.w_len
+            sel_extra["w_len"] = self.w_len
         if self.use_ctc:
             r_prev = None if first else st["r_prev"][k]
+            ctc_kw = dict(n=R, out_len=0, out_len_dev=st["pos"], per_row=st["per_row"], blank=self.blank, eos=self.eos,
+                          uidx=st["uidx"], tlen=st["tlen"])
             if not self.use_dec:
-                self._ctc_full_vocab(st, r_prev)
-            ops.ctc_prefix(st["logp"], r_prev, st["tok"], ids, st["r_new"], st["psi"], n=R, out_len=0,
-                           out_len_dev=st["pos"], per_row="rowpos" in st, blank=self.blank, eos=self.eos,
-                           uidx=st["uidx"], tlen=st["tlen"])
+                self._ctc_full_vocab(st, r_prev, ctc_kw)
+            ops.ctc_prefix(st["logp"], r_prev, st["tok"], ids, st["r_new"], st["psi"], **ctc_kw)
         out = st["out"]
         ops.beam_select(dec, self.n_vocab, ids, st["psi"], st["s_prev"], st["score"], out, n=R, beam=beam,
-                        blank=self.blank, eos=self.eos, w_dec=self.w_dec, w_ctc=self.w_ctc, seg=st["seg"], **sel_hw)
+                        blank=self.blank, eos=self.eos, w_dec=self.w_dec, w_ctc=self.w_ctc, seg=st["seg"], **sel_extra)
         if hw is not None:
-            post_hw = dict(sel_bonus=out["bonus"], sel_next=out["next"], shw=hw["shw"], end_hw=hw["end_hw"],
-                           node_out=hw["node"][1 - k])
+            post_extra = dict(sel_bonus=out["bonus"], sel_next=out["next"], shw=hw["shw"], end_hw=hw["end_hw"],
+                              node_out=hw["node"][1 - k])
         if lm is not None and "arrays" in lm:
-            post_hw.update(sel_lm=out["lm"], sel_lm_next=out["lm_next"], slm=lm["slm"], end_lm=lm["end_lm"],
-                           lm_state_out=lm["state"][1 - k], lm_start=lm["arrays"]["start"])
+            post_extra.update(sel_lm=out["lm"], sel_lm_next=out["lm_next"], slm=lm["slm"], end_lm=lm["end_lm"],
+                              lm_state_out=lm["state"][1 - k], lm_start=lm["arrays"]["start"])
         if lm is not None and "slen" in lm:
-            post_hw.update(slen=lm["slen"], end_len=lm["end_len"])
+            post_extra.update(slen=lm["slen"], end_len=lm["end_len"])
         ops.beam_post(U=st["U"], beam=beam, P=P, R=R, Lmax=st["Lmax"], steps_cap=st["steps"], eos=self.eos,
                       end_detect=st["end_detect"], d_end=float(D_END), pos=st["pos"], maxlen=st["maxlen"],
                       sel_prev=out["prev"], sel_tok=out["tok"], sel_col=out["col"], sel_score=out["score"],
@@ -349,7 +350,7 @@ class BatchBeamSearch:
                       sdec=st["sdec"], sctc=st["sctc"], s_prev=st["s_prev"], src=st["src"], bp_prev=st["bp_prev"],
                       bp_tok=st["bp_tok"], end_flag=st["end_flag"], end_score=st["end_score"], end_dec=st["end_dec"],
                       end_ctc=st["end_ctc"], best_len=st["best_len"], best_end=st["best_end"], done=st["done"],
-                      upos=st.get("upos"), rowpos=st.get("rowpos"), **post_hw)
+                      upos=st.get("upos"), rowpos=st.get("rowpos"), **post_extra)
         Lm, Tm = st["Lmax"], st["Tm"]
         ops.gather_rows(st["anc"][k], st["anc"][1 - k], st["src"][:R], groups=1, n=R, row_bytes=Lm * 4,
                         src_gstride=0, src_rstride=Lm * 4, dst_gstride=0, dst_rstride=Lm * 4)
@@ -380,27 +381,17 @@ class BatchBeamSearch:
             return []
         Ts = [int(x.shape[0]) for x in xs]
         Tm = max(Ts)
-        maxlens = [T if maxlenratio == 0 else (-int(maxlenratio) if maxlenratio < 0 else max(1, int(maxlenratio * T)))
-                   for T in Ts]
+        maxlens = [self._maxlen(T, maxlenratio) for T in Ts]
         D = eng.dD
-        ar = eng.arena
         # padded memory [U][Tm][D] -> CTC log-probs [U][Tm][V] and per-layer cross K/V [U*Tm][2D]
         xp = torch.zeros(U, Tm, D, device=dev, dtype=eng.dtype)
         for u, x in enumerate(xs):      # (the cast kernel converts fp32 encoder outputs to bf16 if needed)
             ops.cast(x.to(dev).reshape(Ts[u], D).contiguous(), xp[u, :Ts[u]])
-        # the CTC head and the cross-attention K / V projections run per utterance (M = T_u rows,
-        # as in the one-utterance call): the few-row and tiled GEMM cores round differently, so
-        # one launch over all U * Tm rows would make an utterance's scores depend on the batch
         cl = torch.zeros(U * Tm, eng.Vp, device=dev, dtype=eng.dtype)
         mem = [torch.zeros(U * Tm, 2 * D, device=dev, dtype=eng.dtype) for _ in range(eng.dl)]
         for u in range(U):
-            xu, r0 = xp[u, :Ts[u]], u * Tm
-            ops.linear_fwd(xu, eng.w("ctc.ctc_lo.weight"), ar.master("ctc.ctc_lo.bias"), out=cl[r0:r0 + Ts[u], :eng.V])
-            for i in range(eng.dl):
-                ca = f"decoder.decoders.{i}.src_attn."
-                ops.linear_fwd(xu, ar.span([ca + "linear_k.weight", ca + "linear_v.weight"]),
-                               ar.span([ca + "linear_k.bias", ca + "linear_v.bias"], buf="master"),
-                               out=mem[i][r0:r0 + Ts[u]])
+            self._project_memory(eng, xp[u, :Ts[u]], cl[u * Tm:u * Tm + Ts[u]], mem, u * Tm)
+        # one log-softmax over all U * Tm rows: the padding rows (zero logits) get finite log-probs
         logp = torch.empty(U, Tm, eng.V, device=dev, dtype=torch.float32)
         ops.log_softmax_rows(cl, eng.V, logp.view(U * Tm, eng.V))
         steps = max(maxlens)
@@ -417,6 +408,20 @@ class BatchBeamSearch:
                     break
         torch.cuda.current_stream(dev).synchronize()
         return self._collect(st, xs, maxlenratio, minlenratio)
+
+    def _project_memory(self, eng, xu, cl, mem, r0):
+        """The CTC head and the cross-attention K / V projections of one utterance xu (T, D), already
+        cast to the engine's dtype: logits into cl (its T rows), layer i's K / V into
+        mem[i][r0:r0 + T]. Per utterance (M = T rows, as in the one-utterance call): the few-row and
+        tiled GEMM cores round differently, so one launch over all rows of a batch would make an
+        utterance's scores depend on the batch. The log-softmax stays with the caller: decode_batch
+        runs one over the rows of all utterances, a session one over the slot's T rows."""
+        ar, T = eng.arena, xu.shape[0]
+        ops.linear_fwd(xu, eng.w("ctc.ctc_lo.weight"), ar.master("ctc.ctc_lo.bias"), out=cl[:, :eng.V])
+        for i in range(eng.dl):
+            ca = f"decoder.decoders.{i}.src_attn."
+            ops.linear_fwd(xu, ar.span([ca + "linear_k.weight", ca + "linear_v.weight"]),
+                           ar.span([ca + "linear_k.bias", ca + "linear_v.bias"], buf="master"), out=mem[i][r0:r0 + T])
 
     def _new_state(self, device, dtype, Ts, maxlens, logp, mem, D, layers, end_detect=1, fold=None):
         """the device-side search state of U = len(Ts) utterances (Ts frames, maxlens steps each)
@@ -437,7 +442,7 @@ class BatchBeamSearch:
         score0 = torch.full((R,), float("-inf"))
         score0[::beam] = 0.0                  # one live hypothesis (sos) per utterance
         st = dict(
-            U=U, R=R, Lmax=Lmax, Tm=Tm, steps=steps, end_detect=int(end_detect), mem=mem, logp=logp,
+            U=U, R=R, Lmax=Lmax, Tm=Tm, steps=steps, end_detect=int(end_detect), mem=mem, logp=logp, per_row=False,
             pos=torch.zeros(1, **i32), maxlen=torch.tensor(maxlens, dtype=torch.int32).to(dev),
             tok=torch.full((R,), self.sos, **i32), score=score0.to(dev),
             sdec=torch.zeros(R, **f64), sctc=torch.zeros(R, **f64), s_prev=torch.zeros(R, **f32),
@@ -523,9 +528,9 @@ class BatchBeamSearch:
         col = slice(r0, r0 + rows)
         bp_prev, bp_tok, flag, esc, edec, ectc = (st[k][:n, col].cpu().numpy() for k in
                                                   ("bp_prev", "bp_tok", "end_flag", "end_score", "end_dec", "end_ctc"))
-        ehw = st["hw"]["end_hw"][:n, col].cpu().numpy() if "hw" in st else None
-        extra = {name: st["lm"][k][:n, col].cpu().numpy() for name, k in (("lm", "end_lm"), ("length_bonus", "end_len"))
-                 if k in st.get("lm", {})}
+        extra = {name: st[grp][k][:n, col].cpu().numpy() for name, grp, k in
+                 (("hotword", "hw", "end_hw"), ("lm", "lm", "end_lm"), ("length_bonus", "lm", "end_len"))
+                 if k in st.get(grp, {})}
         out = []
         for i in range(n):
             for r in np.nonzero(flag[i])[0].tolist():
@@ -536,8 +541,6 @@ class BatchBeamSearch:
                     h = int(bp_prev[j, h]) - r0
                 yseq = [self.sos] + toks[::-1] + ([self.eos] if flag[i, r] == 2 else [])
                 hyp = dict(yseq=yseq, score=float(esc[i, r]), dec=float(edec[i, r]), ctc=float(ectc[i, r]))
-                if ehw is not None:
-                    hyp["hotword"] = float(ehw[i, r])
                 for name, a in extra.items():
                     hyp[name] = float(a[i, r])
                 out.append((r, self._make_hyp(hyp, self.use_dec, self.use_ctc)))
@@ -575,7 +578,7 @@ class BatchBeamSearch:
 
     @staticmethod
     def _maxlen(T, maxlenratio):
-        """steps of an utterance of T frames (decode_batch's rule)"""
+        """steps of an utterance of T frames"""
         return T if maxlenratio == 0 else (-int(maxlenratio) if maxlenratio < 0 else max(1, int(maxlenratio * T)))
 
     def _session_buffers(self, S, max_frames):
@@ -597,21 +600,14 @@ class BatchBeamSearch:
 
     def _session_admit(self, sess, slot, x):
         """utterance x (T, d) into slot `slot` of the session, eagerly on the current stream: the
-        launches decode_batch makes per utterance (CTC head and cross-attention K / V projections
-        over its own T rows, log-softmax), written into the slot's regions. (The second hook the
+        launches decode_batch makes per utterance (`_project_memory` over its own T rows), written
+        into the slot's regions, and the log-softmax of those T rows. (The second hook the
         scripted-decoder tests replace, see `_session_buffers`.)"""
         eng, st = sess.eng, sess.st
-        ar, D, Tm = eng.arena, eng.dD, st["Tm"]
         T = int(x.shape[0])
-        xu, r0 = sess.xbuf[:T], slot * Tm
-        ops.cast(x.to(eng.device).reshape(T, D).contiguous(), xu)
-        cl = sess.clbuf[:T]
-        ops.linear_fwd(xu, eng.w("ctc.ctc_lo.weight"), ar.master("ctc.ctc_lo.bias"), out=cl[:, :eng.V])
-        for i in range(eng.dl):
-            ca = f"decoder.decoders.{i}.src_attn."
-            ops.linear_fwd(xu, ar.span([ca + "linear_k.weight", ca + "linear_v.weight"]),
-                           ar.span([ca + "linear_k.bias", ca + "linear_v.bias"], buf="master"),
-                           out=st["mem"][i][r0:r0 + T])
+        xu, cl = sess.xbuf[:T], sess.clbuf[:T]
+        ops.cast(x.to(eng.device).reshape(T, eng.dD).contiguous(), xu)
+        self._project_memory(eng, xu, cl, st["mem"], slot * st["Tm"])
         ops.log_softmax_rows(cl, eng.V, st["logp"][slot, :T])
 
     def _new_stream_state(self, device, dtype, S, max_frames, steps, logp, mem, D, layers, end_detect=1, fold=None):
@@ -624,6 +620,7 @@ class BatchBeamSearch:
         R = st["R"]
         st["upos"] = torch.zeros(S, device=device, dtype=torch.int32)
         st["rowpos"] = st["pos"] = torch.zeros(R, device=device, dtype=torch.int32)
+        st["per_row"] = True
         for k in ("bp_prev", "bp_tok", "end_flag", "end_score", "end_dec", "end_ctc"):
             st[k] = torch.zeros(steps + 1, R, device=device, dtype=st[k].dtype)
         for k in ("ids", "klen_self", "src"):

@@ -1091,7 +1091,7 @@ def adamw(param, grad, exp_avg, exp_avg_sq, *, lr, beta1, beta2, eps, weight_dec
 
 
 # ---------------------------------------------------------------------------------------
-# Beam-search decode (decode.hip)
+# Beam-search decode (decode_softmax.hip, dec_attn.hip, ctc_prefix.hip, beam.hip)
 # ---------------------------------------------------------------------------------------
 
 def log_softmax_rows(x, V, out):
@@ -1101,12 +1101,12 @@ def log_softmax_rows(x, V, out):
 
 
 _DA_WS = {}
-DA_WAVES = 8               # waves per dec_attn workgroup (decode.hip)
+DA_WAVES = 8               # waves per dec_attn workgroup (dec_attn.hip)
 
 
 def dec_attn_group_fits(klen_max, group):
     """the grouped dec_attn keeps [group][klen_max rounded to 4] scores plus [8][group][64]
-    partials in 64 KiB of LDS (decode.hip avsr_dec_attn); beyond that the kernel refuses"""
+    partials in 64 KiB of LDS (dec_attn.hip avsr_dec_attn); beyond that the kernel refuses"""
     kpad = (int(klen_max) + 3) & ~3
     return (group * kpad + DA_WAVES * group * 64) * 4 <= 64 * 1024
 

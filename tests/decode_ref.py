@@ -1,5 +1,5 @@
-"""Plain CPU references of the beam-search kernels (decode.hip), written from the contract in
-include/avsr_hip.h: numpy / torch fp64 or exact integer logic, no project kernel and nothing of
+"""Plain CPU references of the beam-search kernels (decode_softmax.hip, dec_attn.hip,
+ctc_prefix.hip, beam.hip), written from the contract in include/avsr_hip.h: numpy / torch fp64 or exact integer logic, no project kernel and nothing of
 avsr_amd.ops. Shared by tests/test_gpu_decode_kernels.py (kernel by kernel),
 tests/test_gpu_decode_scripted.py (the real step sequence on a table decoder) and
 tests/test_decode_scripted_cases.py (what the scripted cases cover, from the reference alone)."""

@@ -110,36 +110,57 @@ def hotword_step_ref(trie, nodes, ids_pre, beta, blank=0):
 
 
 # ------------------------------------------------------------------------------ beam_select
-def beam_select_bonus_ref(dec, ids, psi, s_prev, score, bonus, nxt, *, beam, blank, eos, w_dec, w_ctc, seg=None):
+def beam_select_bonus_ref(dec, ids, psi, s_prev, score, bonus, nxt, *, beam, blank, eos, w_dec, w_ctc, seg=None,
+                          lm=None, lm_next=None, w_lm=0.0, w_len=0.0):
     """decode_ref.beam_select_ref with the hot-word bonus: weighted = w_dec*dec + w_ctc*(psi - s_prev)
     + bonus + score, the fp32 sums in this order; the bonus of token v of row h is bonus[h][c], c its
     first column in ids[h], or P (the eos column) for eos, blank and every token outside ids[h].
-    Returns the seven outputs of beam_select_ref plus "bonus" and "next"."""
+    With an n-gram LM (lm / lm_next (n, P + 1)) or a length bonus (w_len != 0) the sum takes the
+    order include/avsr_hip.h states: w_dec*dec + w_len + w_lm*lm + w_ctc*(psi - s_prev) [+ bonus] +
+    score; the LM column of v is its first column in ids[h], P for eos, and none for blank and every
+    token outside ids[h]: an LM term of 0 and a successor of -1. bonus None: no bonus term.
+    Returns the seven outputs of beam_select_ref plus "bonus" and "next" (with bonus) and "lm" and
+    "lm_next" (with lm)."""
     n, V = dec.shape
     P = ids.shape[1]
     f = np.float32
     segs = [0, n] if seg is None else list(seg)
-    keys = ("prev", "tok", "col", "score", "dec", "ctc", "s", "bonus", "next")
+    keys = ("prev", "tok", "col", "score", "dec", "ctc", "s") + (("bonus", "next") if bonus is not None else ()) + \
+        (("lm", "lm_next") if lm is not None else ())
+    filler = dict(prev=None, tok=eos, col=P - 1, score=NEG_INF, dec=0.0, ctc=0.0, s=0.0, bonus=0.0, next=0, lm=0.0,
+                  lm_next=-1)
     out = {k: [] for k in keys}
     for u in range(len(segs) - 1):
         r0, r1 = segs[u], segs[u + 1]
         if all(score[h] == NEG_INF for h in range(r0, r1)):
             for _ in range(beam):
-                for k, v in zip(keys, (r0, eos, P - 1, NEG_INF, 0.0, 0.0, 0.0, 0.0, 0)):
-                    out[k].append(v)
+                for k in keys:
+                    out[k].append(r0 if k == "prev" else filler[k])
             continue
         full_psi = np.full((r1 - r0, V), f(LOGZERO), dtype=f)
         bcol = np.full((r1 - r0, V), P, dtype=np.int64)
+        lcol = np.full((r1 - r0, V), -1, dtype=np.int64)
         for h in range(r0, r1):
             for c in range(P - 1, -1, -1):                       # (first column wins on a repeat)
                 full_psi[h - r0, ids[h, c]] = psi[h, c]
                 if ids[h, c] not in (eos, blank):
-                    bcol[h - r0, ids[h, c]] = c
+                    bcol[h - r0, ids[h, c]] = lcol[h - r0, ids[h, c]] = c
             full_psi[h - r0, eos] = psi[h, P]
             full_psi[h - r0, blank] = f(LOGZERO)
-        full_b = np.stack([bonus[h].astype(f)[bcol[h - r0]] for h in range(r0, r1)])
+            lcol[h - r0, eos] = P
         sp, sc = s_prev[r0:r1, None].astype(f), score[r0:r1, None].astype(f)
-        weighted = ((f(w_dec) * dec[r0:r1].astype(f) + f(w_ctc) * (full_psi - sp)).astype(f) + full_b).astype(f) + sc
+        weighted = f(w_dec) * dec[r0:r1].astype(f)
+        if lm is not None or w_len != 0.0:
+            weighted = (weighted + f(w_len)).astype(f)
+            if lm is not None:
+                full_lm = np.stack([np.where(lcol[h - r0] >= 0, lm[h].astype(f)[lcol[h - r0]], f(0.0))
+                                    for h in range(r0, r1)]).astype(f)
+                weighted = (weighted + f(w_lm) * full_lm).astype(f)
+        weighted = (weighted + f(w_ctc) * (full_psi - sp)).astype(f)
+        if bonus is not None:
+            full_b = np.stack([bonus[h].astype(f)[bcol[h - r0]] for h in range(r0, r1)])
+            weighted = (weighted + full_b).astype(f)
+        weighted = weighted + sc
         weighted[score[r0:r1] == NEG_INF] = NEG_INF
         flat = weighted.reshape(-1)
         order = np.lexsort((np.arange(flat.size), -flat.astype(np.float64)))[:beam]
@@ -147,10 +168,15 @@ def beam_select_bonus_ref(dec, ids, psi, s_prev, score, bonus, nxt, *, beam, bla
             hl, tok = fl // V, fl % V
             h = r0 + hl
             hit = np.nonzero(ids[h] == tok)[0]
-            for k, v in zip(keys, (h, tok, int(hit[0]) if len(hit) else P - 1, float(flat[fl]), float(dec[h, tok]),
-                                   float(f(full_psi[hl, tok]) - f(s_prev[h])), float(full_psi[hl, tok]),
-                                   float(full_b[hl, tok]), int(nxt[h, bcol[hl, tok]]))):
-                out[k].append(v)
+            lc = int(lcol[hl, tok])
+            row = dict(prev=h, tok=tok, col=int(hit[0]) if len(hit) else P - 1, score=float(flat[fl]),
+                       dec=float(dec[h, tok]), ctc=float(f(full_psi[hl, tok]) - f(s_prev[h])), s=float(full_psi[hl, tok]))
+            if bonus is not None:
+                row.update(bonus=float(full_b[hl, tok]), next=int(nxt[h, bcol[hl, tok]]))
+            if lm is not None:
+                row.update(lm=float(lm[h, lc]) if lc >= 0 else 0.0, lm_next=int(lm_next[h, lc]) if lc >= 0 else -1)
+            for k in keys:
+                out[k].append(row[k])
     return out
 
 

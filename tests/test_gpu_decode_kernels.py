@@ -1,5 +1,5 @@
-"""The device-side beam-search kernels (decode.hip), one by one, against the plain references of
-tests/decode_ref.py (fp64 / exact integer logic written from include/avsr_hip.h) and the CPU
+"""The device-side beam-search kernels (decode_softmax.hip, dec_attn.hip, ctc_prefix.hip,
+beam.hip), one by one, against the plain references of tests/decode_ref.py (fp64 / exact integer logic written from include/avsr_hip.h) and the CPU
 oracle's CTC prefix scorer: both CTC prefix kernels with the batched fields, beam selection with
 true ties, the bookkeeping state machine, the one-query attention's kmap / bf16 / partial-group /
 key-split paths, top-k ties, and the exact data movers."""

@@ -37,10 +37,10 @@ frontend.hip video_normalize               1,048,576 x4  11.6 M (6000 x 88 x 22)
 augment.hip  rgb_to_gray                   1,048,576     3.46 M (375 x 96 x 96)        test_rgb_to_gray_above_cap (here)
 gemm.hip   slab_reduce                     1,048,576 x4  <= 1,048,576 (4096 x 1024     at the cap, not above; test_gpu_gemm::
                                            per batch     weight gradient)              test_gemm_layouts_bf16[6000-1024-512-2] is above
-decode.hip beam_kv_put                     262,144       10,240 (80 x 1024 / 8)        below the cap at beam-5 (above it only for fp32 with
+beam.hip beam_kv_put                       262,144       10,240 (80 x 1024 / 8)        below the cap at beam-5 (above it only for fp32 with
                                                                                        > 1024 rows): test_beam_kv_put_above_cap (here)
-decode.hip gather_rows (16-byte words)     524,288       <= 60,000 (80 rows x 750 x 4  below the cap at beam-5 (above it from 700 rows of
-decode.hip gather_rows (4-byte words)      524,288       bytes)                        375 frames): test_gather_rows_above_cap (here)
+beam.hip gather_rows   (16-byte words)     524,288       <= 60,000 (80 rows x 750 x 4  below the cap at beam-5 (above it from 700 rows of
+beam.hip gather_rows   (4-byte words)      524,288       bytes)                        375 frames): test_gather_rows_above_cap (here)
 attention.hip attn_bwd_prep                524,288       96,000 (16 x 375 x 16)        below the cap; test_gpu_attention (f32 / tiled backward)
 conv.hip   stem weight-grad reduce         262,144 x4    6,272 x4 (64 x 392)           below the cap; test_gpu_conv (stem weight gradient)
 conv.hip   conv weight-grad slab reduce    262,144 x4    589,824 x4 (3 x 3 x 512 x     test_gpu_conv (weight gradient at 3 x 3 x 512 x 512)

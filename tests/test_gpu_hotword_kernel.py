@@ -1,5 +1,5 @@
 """The hot-word step kernel (avsr_hotword_step) and avsr_beam_select with its bonus array alone,
-against the restatements in tests/hotword_ref.py: R = 7 rows, P = 4 pre-beam ids, C = 8
+with an LM column alone and with both (candidates pass and full scan), against the restatements in tests/hotword_ref.py: R = 7 rows, P = 4 pre-beam ids, C = 8
 continuation columns, V = 12, beta = 0.75 (every bonus a multiple of 1/4: exact in fp32)."""
 import numpy as np
 import pytest
@@ -107,16 +107,20 @@ def _select_inputs(seed, spread):
                 s_prev=_quant(g, (n,), -3, 0.0), score=score, bonus=bonus, next=nxt)
 
 
-def _select_launch(dev, c, beam, seg, with_bonus):
+def _select_launch(dev, c, beam, seg, with_bonus, with_lm=False, w_ctc=0.5, **fusion):
     nseg = len(seg) - 1
-    out = {**{k: torch.full((nseg * beam,), -77, dtype=torch.int32, device=dev) for k in ("prev", "tok", "col", "next")},
-           **{k: torch.full((nseg * beam,), float("nan"), device=dev) for k in ("score", "dec", "ctc", "s", "bonus")}}
+    out = {**{k: torch.full((nseg * beam,), -77, dtype=torch.int32, device=dev)
+              for k in ("prev", "tok", "col", "next", "lm_next")},
+           **{k: torch.full((nseg * beam,), float("nan"), device=dev)
+              for k in ("score", "dec", "ctc", "s", "bonus", "lm")}}
     dec = torch.zeros(c["dec"].shape[0], V + 3)                  # ld > V
     dec[:, :V] = torch.from_numpy(c["dec"])
     kw = dict(bonus=_f32(c["bonus"], dev), nxt=_i32(c["next"], dev)) if with_bonus else {}
+    if with_lm:
+        kw.update(lm=_f32(c["lm"], dev), lm_next=_i32(c["lm_next"], dev))
     ops.beam_select(dec.to(dev), V, _i32(c["ids"], dev), _f32(c["psi"], dev), _f32(c["s_prev"], dev),
-                    _f32(c["score"], dev), out, n=c["dec"].shape[0], beam=beam, blank=0, eos=EOS, w_dec=0.5, w_ctc=0.5,
-                    seg=_i32(seg, dev), **kw)
+                    _f32(c["score"], dev), out, n=c["dec"].shape[0], beam=beam, blank=0, eos=EOS, w_dec=0.5, w_ctc=w_ctc,
+                    seg=_i32(seg, dev), **kw, **fusion)
     return {k: v.cpu().tolist() for k, v in out.items()}
 
 
@@ -140,4 +144,56 @@ def test_beam_select_with_bonus(dev, beam, seed, spread):
     for k in plain:
         assert got0[k] == plain[k], (k, got0[k], plain[k])
     assert got0["next"] == [-77] * (3 * beam) and all(np.isnan(v) for v in got0["bonus"])
+    assert got0["lm_next"] == [-77] * (3 * beam) and all(np.isnan(v) for v in got0["lm"])
     assert want["tok"] != plain["tok"] or want["prev"] != plain["prev"]      # the bonus does change the pick
+
+
+LM_SEED, LM_SPREAD = 11, 2.0
+
+
+def _lm_inputs():
+    """_select_inputs plus LM scores in [-4, 0] (multiples of 1/4) and arbitrary successors per column"""
+    c = _select_inputs(LM_SEED, LM_SPREAD)
+    g = torch.Generator().manual_seed(LM_SEED + 100)
+    shape = c["bonus"].shape
+    c["lm"] = _quant(g, shape, -4, 0.25)
+    c["lm_next"] = torch.randint(0, 1000, shape, generator=g, dtype=torch.int32).numpy()
+    return c
+
+
+def test_lm_changes_the_reference_picks():
+    """(no kernel) at the seed of the test below the reference picks with the LM differ from those
+    without it, in every case and at both beams: a dropped LM term would show"""
+    seg = [0, 3, 6, 7]
+    c = _lm_inputs()
+    assert c["lm"].min() >= -4.0 and c["lm"].max() <= 0.0 and c["lm_next"].min() >= 0
+    for beam in (3, 5):
+        for with_bonus, w_ctc in ((False, 0.5), (True, 0.5), (True, 0.0)):
+            kw = dict(beam=beam, blank=0, eos=EOS, w_dec=0.5, w_ctc=w_ctc, seg=seg, w_len=0.25)
+            b = (c["bonus"], c["next"]) if with_bonus else (None, None)
+            on = H.beam_select_bonus_ref(c["dec"], c["ids"], c["psi"], c["s_prev"], c["score"], *b, lm=c["lm"],
+                                         lm_next=c["lm_next"], w_lm=0.5, **kw)
+            off = H.beam_select_bonus_ref(c["dec"], c["ids"], c["psi"], c["s_prev"], c["score"], *b, **kw)
+            assert on["tok"] != off["tok"] or on["prev"] != off["prev"], (beam, with_bonus, w_ctc)
+
+
+@pytest.mark.parametrize("beam", [3, 5])
+@pytest.mark.parametrize("with_bonus,w_ctc", [(False, 0.5), (True, 0.5), (True, 0.0)],
+                         ids=["lm", "bonus_lm", "bonus_lm_full_scan"])
+def test_beam_select_with_lm(dev, beam, with_bonus, w_ctc):
+    """avsr_beam_select with an n-gram LM column (w_lm = 0.5, lm_hi = 0) and a length bonus (w_len =
+    0.25) over the layout of the test above: the LM alone, the bonus and the LM together, and both
+    with w_ctc = 0, where the kernel scans every (row, token) from the start, tokens outside ids[h]
+    included (LM term 0, successor -1, the eos column's bonus). All eleven outputs equal the
+    reference that sums in the documented order (the LM alone leaves "bonus" / "next" untouched)."""
+    seg = [0, 3, 6, 7]
+    c = _lm_inputs()
+    b = (c["bonus"], c["next"]) if with_bonus else (None, None)
+    want = H.beam_select_bonus_ref(c["dec"], c["ids"], c["psi"], c["s_prev"], c["score"], *b, beam=beam, blank=0, eos=EOS,
+                                   w_dec=0.5, w_ctc=w_ctc, seg=seg, lm=c["lm"], lm_next=c["lm_next"], w_lm=0.5, w_len=0.25)
+    got = _select_launch(dev, c, beam, seg, with_bonus, True, w_ctc, w_lm=0.5, w_len=0.25, lm_hi=0.0)
+    assert len(want) == (11 if with_bonus else 9)
+    for k in want:
+        assert got[k] == want[k], (k, got[k], want[k])
+    if not with_bonus:
+        assert got["next"] == [-77] * (3 * beam) and all(np.isnan(v) for v in got["bonus"])
