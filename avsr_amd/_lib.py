@@ -145,6 +145,10 @@ class CtcAlignParams(ctypes.Structure):
     ]
 
 
+class CtcAlignGapsParams(ctypes.Structure):
+    _fields_ = CtcAlignParams._fields_ + [("gap", _c_p), ("filler", _c_p), ("gap_penalty", _f)]
+
+
 class CtcNeighborsParams(ctypes.Structure):
     _fields_ = [
         ("dtype", _i), ("B", _i), ("T", _i), ("V", _i), ("Lmax", _i), ("blank", _i), ("eos", _i),
@@ -362,6 +366,7 @@ SYMBOLS = {
     "avsr_ctc_bwd": ([ctypes.POINTER(CtcParams), _c_p], _i),
     "avsr_ctc_align": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
     "avsr_ctc_align_long": ([ctypes.POINTER(CtcAlignParams), _c_p], _i),
+    "avsr_ctc_align_gaps": ([ctypes.POINTER(CtcAlignGapsParams), _c_p], _i),
     "avsr_ctc_neighbors": ([ctypes.POINTER(CtcNeighborsParams), _c_p], _i),
     "avsr_ctc_beam": ([ctypes.POINTER(CtcBeamParams), _c_p], _i),
     "avsr_ctc_kws": ([ctypes.POINTER(CtcKwsParams), _c_p], _i),

@@ -20,7 +20,10 @@
 //   a chunk of n frames that ends in state s only the columns [s - 2(n - 1), s] matter; the block
 //   copies that window of the chunk's rows to LDS as dwords (16 states each), one lane walks it,
 //   the block writes the chunk's tokens together.
+// avsr_ctc_align_gaps is the same kernel with GAPS = true: flagged blank states may read a frame as
+//   the caller's filler (free ends and gaps for transcripts that cover part of a recording).
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -32,8 +35,14 @@ constexpr int BT_W = BT_FRAMES / 8 + 2;     // dwords of a pointer row that a ch
 // bytes of one frame's pointer row: 2 bits per state, padded to 16 bytes
 __host__ __device__ inline int row_bytes(int Lmax) { return ((2 * Lmax + 1 + 63) >> 6) << 4; }
 
-template <typename T, int P, int D>
-__global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_params p) {
+// GAPS: avsr_ctc_align_gaps. A flagged blank state may emit filler[t] + gap_penalty instead of the
+// blank's log-probability; everything it adds is behind `if constexpr (GAPS)`, so the GAPS = false
+// instantiations are the code of before.
+template <bool GAPS>
+using params_t = std::conditional_t<GAPS, avsr_ctc_align_gaps_params, avsr_ctc_align_params>;
+
+template <typename T, int P, int D, bool GAPS>
+__global__ __launch_bounds__(NT) void ctc_align_long_kernel(params_t<GAPS> p) {
   constexpr int H = P / 2;                  // labels per thread
   const int b = blockIdx.x, tid = threadIdx.x;
   const int L = p.label_len[b], Tb = min(p.in_len[b], p.T), S = 2 * L + 1;
@@ -55,6 +64,7 @@ __global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_param
   const bool active = shape_ok && s0 < S;
   uint32_t ko[H];                           // byte offset of each label's logit in a row of x
   uint32_t skipm = 0;                       // bit h: the label state 2h + 1 may be entered from s - 2
+  uint32_t gapm = 0;                        // GAPS, bit h: the blank state 2h (position l0 + h) is a gap state
   if (shape_ok) {
     bool mybad = false;
     int prev = p.blank;
@@ -71,6 +81,12 @@ __global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_param
       prev = k;
     }
     if (mybad) bad = 1;
+    if constexpr (GAPS) {
+      const unsigned char* gap = p.gap + (int64_t)b * (p.Lmax + 1);
+#pragma unroll
+      for (int h = 0; h < H; ++h)
+        if (l0 + h <= L && gap[l0 + h]) gapm |= 1u << h;      // position L is state S - 1
+    }
   }
   __syncthreads();
   auto infeasible = [&]() {
@@ -81,6 +97,7 @@ __global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_param
 
   // emissions of D frames in registers: slot u holds frame t with t % D == u
   float ex[D][H], eb[D], el[D];
+  float eg[GAPS ? D : 1];                   // GAPS: the frame's filler
   auto fetch = [&](int f, int u) {
     if (!active) return;
     f = min(f, Tb - 1);                     // clamped, not branched around: never out of bounds
@@ -96,6 +113,7 @@ __global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_param
     }
     eb[u] = to_f(row[p.blank]);
     el[u] = LSE[f];
+    if constexpr (GAPS) eg[u] = p.filler[(int64_t)b * p.T + f];
   };
   float d[P];
 #pragma unroll
@@ -107,11 +125,17 @@ __global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_param
       if (t < Tb) {                         // uniform over the block
         if (active) {
           const float lse = el[u], ebk = eb[u] - lse;
+          float egm = ebk;                  // GAPS: what a gap state emits, ef where ef > eb (strictly)
+          if constexpr (GAPS) {
+            const float egk = eg[u] + p.gap_penalty;
+            if (egk > ebk) egm = egk;
+          }
           if (t == 0) {
 #pragma unroll
             for (int j = 0; j < P; ++j) d[j] = NINF;
             if (tid == 0) {
               d[0] = ebk;
+              if constexpr (GAPS) if (gapm & 1u) d[0] = egm;
               if (S > 1) d[1] = ex[u][0] - lse;
             }
           } else {
@@ -125,6 +149,7 @@ __global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_param
               uint32_t k = 0;
               if (c1 > m) { m = c1; k = 1; }
               float es = ebk;
+              if constexpr (GAPS) if (!(j & 1) && ((gapm >> (j >> 1)) & 1u)) es = egm;
               if (j & 1) {
                 const float c2r = j >= 2 ? d[j - 2] : left;
                 const float c2 = (skipm >> (j >> 1)) & 1u ? c2r : NINF;
@@ -185,21 +210,31 @@ __global__ __launch_bounds__(NT) void ctc_align_long_kernel(avsr_ctc_align_param
     __syncthreads();
     for (int i = tid; i < n; i += NT) {
       const int s = path[i];
-      ALI[c0 + i] = (s & 1) ? lab[s >> 1] : p.blank;
+      int tok = (s & 1) ? lab[s >> 1] : p.blank;
+      if constexpr (GAPS) {
+        // the DP's own operands and fp32 operations, so the mark agrees with the score
+        const int t = c0 + i;
+        if (!(s & 1) && p.gap[(int64_t)b * (p.Lmax + 1) + (s >> 1)] &&
+            p.filler[(int64_t)b * p.T + t] + p.gap_penalty > to_f(X[(int64_t)t * p.ldx + p.blank]) - LSE[t])
+          tok = AVSR_CTC_ALIGN_GAP;
+      }
+      ALI[c0 + i] = tok;
     }
   }
 }
 
-template <typename T, int P, int D>
-void launch(const avsr_ctc_align_params* p, void* stream) {
-  hipLaunchKernelGGL((ctc_align_long_kernel<T, P, D>), dim3(p->B), dim3(NT), 0, (hipStream_t)stream, *p);
+template <typename T, int P, int D, bool GAPS>
+void launch(const params_t<GAPS>* p, void* stream) {
+  hipLaunchKernelGGL((ctc_align_long_kernel<T, P, D, GAPS>), dim3(p->B), dim3(NT), 0, (hipStream_t)stream, *p);
 }
 
-}  // namespace
-
-extern "C" int avsr_ctc_align_long(const avsr_ctc_align_params* p, void* stream) {
+// the argument checks and the choice of P that both entry points share
+template <bool GAPS>
+int run(const params_t<GAPS>* p, void* stream) {
   if (!p || p->B < 0 || p->T < 0 || p->Lmax < 0 || p->V <= 0 || p->ldx < p->V || p->blank < 0 || p->blank >= p->V)
     return AVSR_E_ARG;
+  if constexpr (GAPS)
+    if (!(p->gap_penalty <= 0.f)) return AVSR_E_ARG;            // NaN or > 0
   return avsr_by_dtype(p->dtype, [&](auto t) -> int {
     using T = decltype(t);
     if (p->Lmax > AVSR_CTC_ALIGN_LONG_LMAX) return AVSR_E_SHAPE;
@@ -207,14 +242,22 @@ extern "C" int avsr_ctc_align_long(const avsr_ctc_align_params* p, void* stream)
     if (!p->label_len || !p->in_len || !p->ali || !p->score || !p->feasible || (p->Lmax > 0 && !p->labels))
       return AVSR_E_ARG;
     if (p->T > 0 && (!p->x || !p->lse || !p->ws)) return AVSR_E_ARG;
+    if constexpr (GAPS)
+      if (p->T > 0 && (!p->gap || !p->filler)) return AVSR_E_ARG;
     if (!avsr_aligned16(p->ws)) return AVSR_E_ALIGN;
     static_assert(AVSR_CTC_ALIGN_LONG_WS(1, 1, 100) == 64, "header macro and row_bytes agree");
     const int SS = 2 * p->Lmax + 1;
-    if (SS <= 4 * NT) launch<T, 4, 4>(p, stream);
-    else if (SS <= 8 * NT) launch<T, 8, 4>(p, stream);
-    else if (SS <= 16 * NT) launch<T, 16, 4>(p, stream);
-    else launch<T, 32, 2>(p, stream);
+    if (SS <= 4 * NT) launch<T, 4, 4, GAPS>(p, stream);
+    else if (SS <= 8 * NT) launch<T, 8, 4, GAPS>(p, stream);
+    else if (SS <= 16 * NT) launch<T, 16, 4, GAPS>(p, stream);
+    else launch<T, 32, GAPS ? 1 : 2, GAPS>(p, stream);      // GAPS at D = 2 spills more
     AVSR_CHECK_LAUNCH();
     return 0;
   });
 }
+
+}  // namespace
+
+extern "C" int avsr_ctc_align_long(const avsr_ctc_align_params* p, void* stream) { return run<false>(p, stream); }
+
+extern "C" int avsr_ctc_align_gaps(const avsr_ctc_align_gaps_params* p, void* stream) { return run<true>(p, stream); }

@@ -27,10 +27,19 @@ clips, or the word times of a caption file.
   engine T * 5056 * 2 B, 300 MB for 20 minutes (T = 30000). The video tensor itself is larger
   (T * 88 * 88 * 4 B = 930 MB as fp32) and may stay on the host: windows are moved group by group.
   The alignment's back-pointers take T * (2 L + 1) / 4 bytes: 90 MB at T = 30000, L = 6000.
-* Out of scope: material at the start or the end of the recording that the transcript does not
-  cover (the Viterbi has fixed ends; a free-start variant is a later change); media decoding and
-  caption-file writing; transcribing the resulting clips (decode_batch / decode_stream on encoder
-  output, as before).
+* A transcript that covers only PART of the recording (an intro before the first transcribed
+  word, applause after the last, passages the transcriber skipped) goes through align_partial
+  (avsr_ctc_align_gaps): the blank before the first token, after the last one and at every listed
+  position between two tokens becomes a gap state, which may read a frame as its best token
+  (max_v logits[t][v] - lse[t]) plus `gap_penalty` where that beats the blank. Such frames are -2
+  in PartialAlignment.ali, their runs are PartialAlignment.gaps, and segments() cuts there and
+  keeps clips out of them. `gap_penalty` is a per-frame log-probability and HAS NO DEFAULT: A USEFUL
+  VALUE, AND THE ACCURACY OF THE RECOVERED BOUNDARIES ON REAL SPEECH, ARE UNMEASURED (no checkpoint
+  or data here).
+* Out of scope: transcript words that were NOT SAID (no state is skippable beyond CTC's own rule,
+  so these still show as low `worst`); media decoding and caption-file writing; transcribing the
+  resulting clips or the uncovered stretches (decode_batch / decode_stream on encoder output, as
+  before).
 """
 from collections import namedtuple
 
@@ -44,6 +53,10 @@ MAX_TOKENS = ops.CTC_ALIGN_LONG_LMAX
 # spans: align.TokenSpans, one per token of y; score: log-probability of the path; frame_logp:
 # (T,) float32 numpy, the path's own log p(ali[t] | x) per frame (it sums to score)
 LongAlignment = namedtuple("LongAlignment", ["spans", "score", "frame_logp"])
+# align_partial's result. spans, score, frame_logp as above (frame_logp[t] = filler[t] + gap_penalty at a
+# gap frame, so it still sums to score); gaps: the maximal runs [start, end) of gap frames, in order; ali:
+# (T,) int32 numpy, the token per frame with ops.CTC_ALIGN_GAP = -2 at gap frames
+PartialAlignment = namedtuple("PartialAlignment", ["spans", "score", "frame_logp", "gaps", "ali"])
 # frames [start, end) of the recording; first / last: indices into y (inclusive); tokens: their ids;
 # text: the words joined by spaces; score / worst: mean frame_logp over the run / of its worst word
 Segment = namedtuple("Segment", ["start", "end", "first", "last", "tokens", "text", "score", "worst"])
@@ -147,6 +160,111 @@ def align_long(e2e, logits, lse, y):
     return LongAlignment(align.token_spans(ali[0].cpu().numpy(), e2e.blank), float(score.item()), flp.cpu().numpy())
 
 
+def _transcript(e2e, y):
+    """y without sos / eos, with align_long's checks but against e2e.odim (the engine's V): no
+    device is needed"""
+    V = e2e.odim
+    y = align.strip_sos_eos(y, e2e.sos, e2e.eos)
+    if any(t < 0 or t >= V for t in y):
+        raise ValueError(f"token id outside [0, {V})")
+    if any(t == e2e.blank or t == e2e.eos for t in y):
+        raise ValueError("blank / eos inside the transcript")
+    if len(y) > MAX_TOKENS:
+        raise ValueError(f"{len(y)} tokens, avsr_ctc_align_long takes at most {MAX_TOKENS}")
+    return y
+
+
+def _frames(logits, lse):
+    T = int(logits.shape[0])
+    if T < 1 or logits.dim() != 2 or tuple(lse.shape) != (T,):
+        raise ValueError(f"logits (T, >= V) and lse (T,), got {tuple(logits.shape)} and {tuple(lse.shape)}")
+    return T
+
+
+def _labels(y, dev):
+    lab = torch.full((1, max(1, len(y))), -1, dtype=torch.int32)
+    lab[0, :len(y)] = torch.tensor(y, dtype=torch.int32)
+    return lab.to(dev), torch.tensor([len(y)], dtype=torch.int32).to(dev)
+
+
+def gap_flags(n_tokens, free_start=True, free_end=True, gaps=()):
+    """the n_tokens + 1 flags of avsr_ctc_align_gaps as a list of 0 / 1: position 0 (free_start),
+    position n_tokens (free_end) and the positions `gaps`, i in 1 .. n_tokens - 1 meaning "between
+    token i - 1 and token i" (0-based tokens), or "all" for every one of them. ValueError: a
+    position outside [1, n_tokens - 1]."""
+    L = int(n_tokens)
+    flags = [0] * (L + 1)
+    if isinstance(gaps, str):
+        if gaps != "all":
+            raise ValueError(f"gaps = {gaps!r}: positions or 'all'")
+        gaps = range(1, L)
+    for i in gaps:
+        if int(i) != i or i < 1 or i > L - 1:
+            raise ValueError(f"gap position {i} outside [1, {L - 1}]")
+        flags[int(i)] = 1
+    if free_start:
+        flags[0] = 1
+    if free_end:
+        flags[L] = 1
+    return flags
+
+
+def _gap_penalty(gap_penalty):
+    g = float(gap_penalty)
+    if not g <= 0.0:
+        raise ValueError(f"gap_penalty = {gap_penalty}: a log-probability per frame, <= 0 (-inf: no gaps)")
+    return g
+
+
+def gap_runs(ali):
+    """maximal [start, end) runs of ops.CTC_ALIGN_GAP in a frame alignment, in order"""
+    edge = np.diff(np.concatenate([[0], (np.asarray(ali) == ops.CTC_ALIGN_GAP).astype(np.int8), [0]]))
+    return [[int(a), int(b)] for a, b in zip(np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0])]
+
+
+@torch.no_grad()
+def align_partial(e2e, logits, lse, y, *, gap_penalty, free_start=True, free_end=True, gaps=()):
+    """align_long for a transcript that covers only part of the recording: the blank before the
+    first token (free_start), after the last one (free_end) and at the positions `gaps` (gap_flags:
+    i in 1 .. len(y) - 1, "between token i - 1 and token i" of y after sos / eos stripping, or
+    "all") is a gap state, which reads frame t as filler[t] + gap_penalty where that is above the
+    blank's log-probability; filler[t] = max_v float(logits[t][v]) - lse[t] is computed on the
+    device from the engine-dtype logits (exact: the maximum of upcast values is the upcast of their
+    maximum; no (T, V) fp32 copy is made). A flagged gap that holds nothing costs nothing.
+    gap_penalty <= 0 (-inf: align_long's result) HAS NO DEFAULT: A USEFUL VALUE IS UNMEASURED, as
+    is the accuracy of the recovered boundaries on real speech (module docstring).
+    Returns PartialAlignment(spans, score, frame_logp, gaps, ali), or None where no alignment
+    exists (fewer frames than tokens + adjacent repeats, as before). ValueError: everything
+    align_long checks, a gap position outside [1, len(y) - 1], gap_penalty NaN or > 0: all before
+    the device is touched. One avsr_ctc_align_gaps launch."""
+    y = _transcript(e2e, y)
+    pen = _gap_penalty(gap_penalty)
+    flags = gap_flags(len(y), free_start, free_end, gaps)
+    T = _frames(logits, lse)
+    eng = e2e.engine()
+    dev = eng.device
+    lab, llen = _labels(y, dev)
+    gap = torch.zeros(1, lab.shape[1] + 1, dtype=torch.uint8)
+    gap[0, :len(y) + 1] = torch.tensor(flags, dtype=torch.uint8)
+    filler = logits[:, :eng.V].amax(1).float() - lse
+    ali, score, feas = ops.ctc_align_gaps(logits, 1, T, eng.V, lab, llen, torch.tensor([T], dtype=torch.int32).to(dev),
+                                          lse, gap.to(dev), filler, pen, blank=e2e.blank)
+    if not int(feas.item()):
+        return None
+    ingap = ali[0] == ops.CTC_ALIGN_GAP
+    tok = torch.where(ingap, torch.full_like(ali[0], e2e.blank), ali[0])
+    flp = torch.where(ingap, filler + pen, logits.gather(1, tok.view(T, 1).long()).view(T).float() - lse)
+    ali = ali[0].cpu().numpy()
+    return PartialAlignment(align.token_spans(tok.cpu().numpy(), e2e.blank), float(score.item()), flp.cpu().numpy(),
+                            gap_runs(ali), ali)
+
+
+def uncovered(alignment):
+    """the stretches of the recording that a PartialAlignment left to its gaps, as (start, end)
+    frame tuples in order: what a caller may want to transcribe (decode_stream on those frames)"""
+    return [(int(a), int(b)) for a, b in alignment.gaps]
+
+
 def segments(alignment, token_list, max_frames=375, margin=5, space="▁"):
     """Cut an aligned recording into clips of at most max_frames frames at its pauses: a list of
     Segments in order, which together hold every token exactly once. Pure host code.
@@ -159,7 +277,15 @@ def segments(alignment, token_list, max_frames=375, margin=5, space="▁"):
     word is split at its widest gap (ties: the earliest), until every run fits or is a single word.
     A SINGLE WORD LONGER THAN max_frames IS RETURNED AS IT IS: filter on end - start.
     score = mean of frame_logp over [start_a, end_b); worst = the minimum over the run's words of
-    the word's mean frame_logp (calibration unmeasured: module docstring). No tokens: []."""
+    the word's mean frame_logp (calibration unmeasured: module docstring). No tokens: [].
+
+    An alignment with a `gaps` attribute (PartialAlignment: runs [start, end) of frames that the
+    transcript does not cover) additionally: every pause that contains a gap run is a cut from
+    the start, whatever max_frames; and a run's extent stays out of gap frames, lo >= the end of the
+    last gap run at or before start_a and hi <= the start of the first gap run at or after end_b
+    (instead of 0 and T at the recording's ends). With gaps == [] the result is that of the same
+    spans as a LongAlignment. score / worst are as above: word frames are never gap frames. A gap
+    run INSIDE a word (between two of its pieces, possible with gaps="all") stays in its clip."""
     spans, flp = alignment.spans, np.asarray(alignment.frame_logp)
     T = len(flp)
     words = align.word_groups([sp.token for sp in spans], token_list, space)
@@ -170,13 +296,18 @@ def segments(alignment, token_list, max_frames=375, margin=5, space="▁"):
     n = len(words)
     gap = [start[i + 1] - end[i] for i in range(n - 1)]
     cut = [end[i] + gap[i] // 2 for i in range(n - 1)]
+    holes = [(int(a), int(b)) for a, b in getattr(alignment, "gaps", ())]
+    floor = [max([b for _, b in holes if b <= start[i]], default=0) for i in range(n)]
+    ceil = [min([a for a, _ in holes if a >= end[i]], default=T) for i in range(n)]
+    forced = [i for i in range(n - 1) if any(a >= end[i] and b <= start[i + 1] for a, b in holes)]
 
     def extent(a, b):
-        lo = max(cut[a - 1] if a > 0 else 0, start[a] - margin)
-        hi = min(cut[b] if b < n - 1 else T, end[b] + margin)
+        lo = max(cut[a - 1] if a > 0 else 0, start[a] - margin, floor[a])
+        hi = min(cut[b] if b < n - 1 else T, end[b] + margin, ceil[b])
         return lo, hi
 
-    runs, todo = [], [(0, n - 1)]
+    firsts = [0] + [i + 1 for i in forced]
+    runs, todo = [], list(zip(firsts, [i for i in forced] + [n - 1]))[::-1]
     while todo:
         a, b = todo.pop()
         lo, hi = extent(a, b)

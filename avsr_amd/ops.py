@@ -751,6 +751,42 @@ def ctc_align_long(x, B, T, V, labels, label_len, in_len, lse, *, blank=0, ali=N
     return ali, score, feasible
 
 
+CTC_ALIGN_GAP = -2             # avsr_ctc_align_gaps: ali of a frame spent in a gap (AVSR_CTC_ALIGN_GAP)
+
+
+def ctc_align_gaps(x, B, T, V, labels, label_len, in_len, lse, gap, filler, gap_penalty, *, blank=0, ali=None,
+                   score=None, feasible=None, ws=None):
+    """ctc_align_long for transcripts that cover only part of their recording (avsr_ctc_align_gaps):
+    gap (B, Lmax + 1) uint8 contiguous flags the blank positions 0 .. label_len[b] that may read a
+    frame as filler[b*T + t] + gap_penalty where that exceeds the blank's log-probability
+    (position 0: a free start, position L: a free end); filler (B*T,) fp32 <= 0; gap_penalty a
+    float <= 0, -inf allowed (NaN or > 0: the launcher's argument error). Such frames are
+    CTC_ALIGN_GAP in ali. Workspace and bound as ctc_align_long."""
+    dev = x.device
+    if labels.dim() != 2:
+        raise ValueError("ctc_align_gaps: labels (B, Lmax)")
+    Lmax = labels.shape[1]
+    if gap.dtype != torch.uint8 or filler.dtype != torch.float32:
+        raise TypeError("ctc_align_gaps: gap uint8, filler fp32")
+    if tuple(gap.shape) != (B, Lmax + 1) or not gap.is_contiguous() or tuple(filler.shape) != (B * T,) \
+            or not filler.is_contiguous():
+        raise ValueError(f"ctc_align_gaps: gap (B, Lmax + 1) = ({B}, {Lmax + 1}) and filler (B*T,) = ({B * T},) "
+                         f"contiguous, got {tuple(gap.shape)} and {tuple(filler.shape)}")
+    if ali is None:
+        ali = torch.empty(B, T, device=dev, dtype=torch.int32)
+    if score is None:
+        score = torch.empty(B, device=dev, dtype=torch.float32)
+    if feasible is None:
+        feasible = torch.empty(B, device=dev, dtype=torch.int32)
+    if ws is None and Lmax <= CTC_ALIGN_LONG_LMAX:      # beyond the bound the launcher returns the shape error
+        ws = torch.empty(max(16, ctc_align_long_ws(B, T, Lmax)), device=dev, dtype=torch.uint8)
+    _call("avsr_ctc_align_gaps", L.fill(L.CtcAlignGapsParams, dtype=dtype_code(x), B=B, T=T, V=V, Lmax=Lmax,
+                                         blank=blank, x=x, ldx=x.stride(0), lse=lse, labels=labels,
+                                         label_len=label_len, in_len=in_len, ws=ws, ali=ali, score=score,
+                                         feasible=feasible, gap=gap, filler=filler, gap_penalty=float(gap_penalty)))
+    return ali, score, feasible
+
+
 def ctc_neighbors_ws(B, T, Lmax):
     """bytes of alpha / beta workspace of ctc_neighbors (AVSR_CTC_NEIGHBORS_WS)"""
     return (B * T * (2 * Lmax + 1) * 2 * 4 + 15) & ~15

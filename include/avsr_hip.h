@@ -588,6 +588,51 @@ int avsr_ctc_align(const avsr_ctc_align_params* p, void* stream);
 int avsr_ctc_align_long(const avsr_ctc_align_params* p, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * avsr_ctc_align_gaps: avsr_ctc_align_long for a transcript that covers only PART of its
+ *   recording (avsr_amd/longform.py, align_partial): material before the first word, after the
+ *   last one, or between two words that nobody transcribed. The gap sits ON THE BLANK STATES, so
+ *   the 2L + 1 topology, the back-pointers, the workspace (AVSR_CTC_ALIGN_LONG_WS, 16-byte
+ *   aligned) and the bound (AVSR_CTC_ALIGN_LONG_LMAX) are those of avsr_ctc_align_long. Inputs
+ *   beyond its:
+ *     gap[b][i], i = 0..label_len[b] (row stride Lmax + 1): non-zero marks the blank state 2i as
+ *       a GAP STATE. Flag 0 frees the start, flag L the end, flag i says that something
+ *       untranscribed may have been said between token i and token i + 1 (1-based tokens).
+ *     filler[b*T + t] (<= 0): the log-probability a gap state may take at frame t instead of the
+ *       blank's; the Python layer passes the greedy reading max_v float(x[t][v]) - lse[t].
+ *     gap_penalty (<= 0, -inf allowed): added to the filler per frame.
+ *   With eb = float(x[t][blank]) - lse[t] and ef = filler[t] + gap_penalty (ONE fp32 add), a gap
+ *   state emits ef where ef > eb (strictly), else eb. That is the only change: every other
+ *   emission, the recursion, the skip rule, the first-maximum back-pointer order (s, s-1, s-2),
+ *   the start states (0, 1), the final-state rule and every infeasibility rule are those of
+ *   avsr_ctc_align; the minimum number of frames stays L + adjacent repeats. A skip across a gap
+ *   state stays legal, so a flagged gap that holds nothing costs nothing.
+ *   ali[b][t] as before, except that a frame spent in a gap state with ef > eb is written as
+ *   AVSR_CTC_ALIGN_GAP; score[b] counts those frames at ef. With all flags 0, or with
+ *   gap_penalty = -inf, ali and score equal avsr_ctc_align_long's bit for bit; a float32 host
+ *   Viterbi reproduces everything bit for bit.
+ *   AVSR_E_ARG beyond avsr_ctc_align_long's: gap or filler NULL with B > 0 and T > 0;
+ *   gap_penalty NaN or > 0. A NaN or positive filler VALUE is not checked: the result for that
+ *   recording is then unspecified (other recordings of the launch are unaffected).
+ *   No allocation, no sync, no atomics.
+ * ------------------------------------------------------------------------------------ */
+#define AVSR_CTC_ALIGN_GAP (-2)
+typedef struct {
+  int dtype, B, T, V, Lmax, blank;     /* the fields of avsr_ctc_align_params ... */
+  const void* x; int64_t ldx;
+  const float* lse;
+  const int* labels;
+  const int* label_len; const int* in_len;
+  unsigned char* ws;                   /* AVSR_CTC_ALIGN_LONG_WS(B, T, Lmax) bytes */
+  int* ali;
+  float* score;
+  int* feasible;
+  const unsigned char* gap;            /* ... followed by: [B][Lmax + 1] */
+  const float* filler;                 /* [B*T] */
+  float gap_penalty;
+} avsr_ctc_align_gaps_params;
+int avsr_ctc_align_gaps(const avsr_ctc_align_gaps_params* p, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * avsr_ctc_neighbors: the exact CTC log-likelihood of every ONE-EDIT NEIGHBOUR of a label
  *   sequence, for B utterances in one call (the reference has no counterpart; token and word
  *   confidences, avsr_amd/confidence.py). For y = y_1..y_L over n = min(in_len[b], T) frames and a
