@@ -405,19 +405,33 @@ __global__ __launch_bounds__(256) void ctc_bwd_kernel(avsr_ctc_params p) {
   const float* G = p.gamma + ((int64_t)b * p.T + t) * SS;
   __shared__ float gsum_blank;
   __shared__ float sh[4];
-  float gb = 0.f;
-  if (active)
+  // The stored fp32 lse is off by up to half an ulp of |lse| (5e-7 at lse ~ 12), and so is
+  // exp(x - lse) where the posterior is near 1 -- there the occupancy is near 1 too and the
+  // gradient is their small difference. Renormalising by the row's own sum of exp(x - lse)
+  // takes the error of lse out (the row is re-read from cache; active rows only).
+  float gb = 0.f, se = 0.f;
+  if (active) {
     for (int s = threadIdx.x * 2; s < S; s += 512) gb += G[s];
+    for (int c0 = threadIdx.x * VE; c0 < p.V; c0 += 256 * VE) {
+      float v[VE];
+      ldv(x + c0, v);
+#pragma unroll
+      for (int j = 0; j < VE; ++j)
+        if (c0 + j < p.V) se += expf(v[j] - lse);
+    }
+  }
   gb = block_sum(gb, sh);
+  se = block_sum(se, sh);
   if (threadIdx.x == 0) gsum_blank = gb;
   __syncthreads();
+  const float inv = active ? 1.f / se : 1.f;
   for (int c0 = threadIdx.x * VE; c0 < p.lddx; c0 += 256 * VE) {
     float v[VE], o[VE];
     if (c0 < p.V) ldv(x + c0, v);
 #pragma unroll
     for (int j = 0; j < VE; ++j) {
       const int c = c0 + j;
-      o[j] = c < p.V ? scale * (expf(v[j] - lse) - (c == 0 ? gsum_blank : 0.f)) : 0.f;
+      o[j] = c < p.V ? scale * (expf(v[j] - lse) * inv - (c == 0 ? gsum_blank : 0.f)) : 0.f;
     }
     stv(dx + c0, o);
   }
@@ -429,7 +443,7 @@ __global__ __launch_bounds__(256) void ctc_bwd_kernel(avsr_ctc_params p) {
     float g = 0.f;
     for (int j = 0; j < L; ++j)
       if (lab[j] == k) g += G[2 * j + 1];
-    const float sm = expf(to_f(x[k]) - lse);
+    const float sm = expf(to_f(x[k]) - lse) * inv;
     dx[k] = from_f<T>(scale * (sm - g));
   }
 }

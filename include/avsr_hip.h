@@ -498,7 +498,8 @@ int avsr_attn_dropmask(const avsr_attn_params* p, void* stream);
  *   (ctc.py:64-81): log-space alpha and beta over the extended label sequence; nll[b] and the
  *   state occupancies gamma[b][t][s] = P(path at state s at t | x) (0 if infeasible)
  * avsr_ctc_bwd:   dx[b,t,k] = (*dloss * coef) * (softmax_t(k) - sum_{s: ext_s = k} gamma_t(s))
- *   for t < in_len[b] (0 otherwise and for infeasible utterances)
+ *   for t < in_len[b] (0 otherwise and for infeasible utterances); softmax_t is exp(x - lse)
+ *   divided by its own row sum, so the rounding of the stored fp32 lse does not reach it
  * avsr_loss_finalize: loss_ctc = sum nll / B, loss_att = sum row_loss / B (att_per_token = 0) or
  *   / the number of target tokens, i.e. rows with row_correct >= 0 (att_per_token = 1:
  *   transformer_length_normalized_loss, label_smoothing_loss.py:61; needs row_correct),

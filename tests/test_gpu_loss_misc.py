@@ -129,6 +129,7 @@ def test_label_smoothing(dev, dtype):
     dx = torch.empty(R, Vp, device=dev, dtype=dtype)
     ops.lsm_bwd(xd, V, tgd, sm, lse, torch.tensor([0.9], device=dev), 1.0 / B, dx)
     assert _rel(dx[:, :V], xr.grad) < (1e-5 if dtype == torch.float32 else 1e-2)
+    assert dx[:, V:].abs().max().item() == 0
     out = torch.empty(4, device=dev)
     nll = torch.tensor([1.0, 2.0, 3.0], device=dev)
     ops.loss_finalize(B, nll, rl, rc, 0.1, out)
